@@ -7,12 +7,14 @@ A "step" is one device-resident simulation::time_step(dt) (reference: src/simula
     -> extrapolation -> G2P
 over the particles resident in HBM. The timed region starts on a dam that is already breaking: at least 20 untimed steps
 (`--warmup`, topped up by a pre-roll when the caller asks for fewer) precede it, so that particles cross cells and tiles, the
-binning permutes, the deferred v/C gather fires and the multigrid tile lists are rebuilt as in a production run. The hot path
-alone (lfa_step_hot: the rows of SURVEY 8(a)) is reported beside it under "hot_path".
+binning permutes, the deferred v/C gather fires and the multigrid tile lists are rebuilt as in a production run. With `--full`
+the hot path alone (lfa_step_hot: the rows of SURVEY 8(a)) is reported beside it under "hot_path".
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches one rank per GPU with
 torch.distributed.run. W untimed steps, then exactly K timed steps bracketed by barrier + device synchronise, MAX over
-ranks, rank 0 prints ONE JSON line.
+ranks, rank 0 prints ONE JSON line. A plain run does only that; `--full` adds every secondary figure (stage attribution loop,
+per-kernel and roofline figures, the hot path alone, the MIC(0) record, the other scaling mode, the CPU baseline).
+`--dump-outputs DIR` writes what the timed step computes from the seeded input (dump_outputs), after everything else.
 """
 import argparse
 import json
@@ -222,6 +224,44 @@ def med(xs):
     return statistics.median(xs) if xs else 0.0
 
 
+def _sample(n, k, seed):
+    """Fixed, seeded choice of min(n, k) of the indices [0, n), ascending."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(sim, outdir, last_step, blo, bhi):
+    """What the step just taken computed, as a caller of lfa_time_step receives it, as DIR/<name>.npy in float64 (at most 42 MB).
+    Every shape follows from the arguments alone, so that two runs or two builds compare array for array:
+      particles: position, velocity and APIC affine columns cx|cy|cz at 2^18 fixed, seeded indices of the upload order (the order
+                 lfa_download_particles keeps whatever the device's binning did), and those indices;
+      pressure:  at 2^19 fixed, seeded cells of the seeded dam-break block [blo, bhi), 0 where the cell holds no fluid (the
+                 reference's pressure outside the unknowns), and those cells' raw indices (x fastest) - the set of fluid cells
+                 itself differs from run to run near the free surface;
+      the step's dt, PCG residual and iterations."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    p, cells = sim.pressure(), sim.fluid_cells()  # cells[i]: raw index (x fastest) of unknown i, ascending
+    assert len(p) == len(cells) > 0, (len(p), len(cells))
+    ext = [int(h) - int(l) for l, h in zip(blo, bhi)]
+    k = _sample(ext[0] * ext[1] * ext[2], 1 << 19, 2)
+    x, y, z = blo[0] + k % ext[0], blo[1] + (k // ext[0]) % ext[1], blo[2] + k // (ext[0] * ext[1])
+    raw = (x + sim.size[0] * (y + sim.size[1] * z)).astype(np.uint64)
+    at = np.minimum(np.searchsorted(cells, raw), len(cells) - 1)
+    pressure = np.where(cells[at] == raw, p[at], 0.0)
+    parts = sim.download_particles()
+    pi = _sample(len(parts), 1 << 18, 1)
+    rec = parts[pi]
+    del parts
+    out = {"particle_index": pi, "position": rec["pos"], "velocity": rec["vel"],
+           "affine": np.stack([rec["cx"], rec["cy"], rec["cz"]], axis=1),
+           "pressure_cell": raw, "pressure": pressure, "step_dt_residual_iterations": np.array(last_step)}
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -269,9 +309,22 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="N > 1: skip the other scaling mode's run (reported under `weak` / `strong`)")
     ap.add_argument("--watchdog-s", type=int, default=1500, help="N > 1: a rank that has printed no result after this many seconds exits with "
                     "code 124 instead of waiting for ever on a peer (0 = off)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure every secondary figure: the stage "
+                    "attribution loop, per-kernel / roofline figures, the hot path alone, the MIC(0) record, the other scaling mode "
+                    "(N > 1) and the CPU baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="at the end, write what one timed step computes from the seeded input as "
+                    "DIR/<name>.npy (float64, a fixed seeded sample of the particles and the pressure; one domain on one GPU)")
     args = ap.parse_args()
     if args.weak and args.strong:
         raise SystemExit("--weak and --strong exclude each other")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_slabs):
+        raise SystemExit("--dump-outputs needs one domain on one GPU (--gpus 1, no --force-slabs)")
+    if not args.full:
+        # a plain run times the steps and prints the line, nothing else
+        args.no_serial_stages = args.no_kernel_timing = args.no_hot_path = args.no_mic0_record = args.no_secondary = True
+        args.no_cpu_baseline = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `--gpus N` without N ranks: this process is not a rank. Start the ranks the way the driver does (nothing here has touched
@@ -342,7 +395,7 @@ def main():
     extras = {}
     if slabs:
         extras["transport"] = transport_used
-    if args.obstacle:
+    def add_obstacle(sim):
         # a sphere in the dry part of the tank, in the path of the collapsing column, voxelized on the device and marked solid
         # without leaving it (it must not overlap the seeded block: particles deep inside a solid give rows without a diagonal)
         rad = 0.16 * min(bhi[0] - blo[0], bhi[1] - blo[1], cfg["block"][1][2] - blo[2])
@@ -351,10 +404,13 @@ def main():
         t0 = time.perf_counter()
         vox = lfa.Voxels.from_mesh(mpos, midx, 1.0, (0.0, 0.0, 0.0), device=local_rank)
         sim.set_solid_from_voxels(vox, True, True)
-        extras["voxelizer"] = {"triangles": int(len(midx) // 3), "voxel_grid": list(vox.size),
-                               "ms_mesh_to_solid_cells": 1e3 * (time.perf_counter() - t0),
-                               "solid_cells": int(len(vox.cells(True, True, size)))}
+        info = {"triangles": int(len(midx) // 3), "voxel_grid": list(vox.size), "ms_mesh_to_solid_cells": 1e3 * (time.perf_counter() - t0),
+                "solid_cells": int(len(vox.cells(True, True, size)))}
         vox.close()
+        return info
+
+    if args.obstacle:
+        extras["voxelizer"] = add_obstacle(sim)
     sim.seed_block(blo, bhi)
     sim.enable_timing(True)
     if args.no_overlap:
@@ -376,11 +432,13 @@ def main():
         return c
 
     marks = []  # host clock each time the CFL read-back returns: the device has finished the step before (one stamp per step)
+    last_step = []  # dt, residual, iterations of the latest step (--dump-outputs)
 
     def one_step():
         dt = min(3.0 * global_cfl(), args.dt_max)
         marks.append(time.perf_counter())
         res, it, rc = sim.time_step(dt)
+        last_step[:] = (dt, res, it)
         return dt, it, rc
 
     preroll = max(0, MIN_LEAD_IN - args.warmup)
@@ -723,6 +781,22 @@ def main():
         sim.synchronize()
         dist.barrier()
     sim.close()
+    if args.dump_outputs:
+        # A full step is not bit-reproducible (the binning orders a tile's particles with atomics, so the position correction sums
+        # its neighbours in another order every run) and a dam break amplifies that: after the lead-in and the timed steps two runs
+        # differ far beyond rounding. What is dumped is therefore the timed step - same handle configuration, same dt rule -
+        # applied to the seeded input, which any two runs and any two builds share exactly.
+        sim, _, _, _, _, _ = build_sim(args, cfg, lfa, torch, dist, tdev, rank, world, local_rank, n_dev, shared_gpu, transport, slabs,
+                                       strong)
+        if args.obstacle:
+            add_obstacle(sim)
+        sim.seed_block(blo, bhi)
+        sim.enable_timing(True)
+        if args.no_overlap:
+            sim.set_step_overlap(False)
+        one_step()
+        dump_outputs(sim, args.dump_outputs, last_step, blo, bhi)
+        sim.close()
     if slabs and world > 1 and not args.no_secondary:
         # the other scaling mode, beside the headline: same step, same lead-in, same barrier + max-over-ranks timing, no stage breakdown
         other = not strong

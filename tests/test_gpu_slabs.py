@@ -777,7 +777,7 @@ def test_bench_runs_n_processes_on_one_gpu(tmp_path):
     env = dict(os.environ, LFA_SHM_SLOT_MB="16")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", "2", "--config", "C2", "--steps", "4", "--warmup", "2", "--transport", "shm",
-           "--no-serial-stages"]
+           "--no-serial-stages", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

@@ -2,7 +2,7 @@
 # tools/ab_env.sh VAR [CONFIGS...] -- A/B of one environment switch on the GPU box: bench.py with VAR unset, then VAR=1.
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
 VAR=$1; shift
-L="--no-cpu-baseline --no-hot-path --no-mic0-record"
+L="--full --no-cpu-baseline --no-hot-path --no-mic0-record"
 for C in ${@:-C4}; do
   for V in default set default set; do
     if [ $V = set ]; then export $VAR=1; else unset $VAR; fi

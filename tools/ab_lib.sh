@@ -3,7 +3,7 @@
 # with the other objects): stage medians of the full step, twice each, alternating.
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
 ALT=$1; shift
-L="--no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
+L="--full --no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
 cp libfluid_amd/libfluid_amd.so /tmp/lfa_keep.so
 for C in ${@:-C4}; do
   for V in base alt base alt; do

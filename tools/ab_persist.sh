@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on the GPU box: the coarse levels of the V-cycle in one launch (default) against a launch per phase (LFA_MG_NO_PERSIST=1).
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
-L="--no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
+L="--full --no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
 for C in C2 C4; do
   for V in persist nopersist; do
     if [ $V = nopersist ]; then export LFA_MG_NO_PERSIST=1; else unset LFA_MG_NO_PERSIST; fi

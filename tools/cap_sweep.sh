@@ -2,7 +2,7 @@
 # LFA_PCG_GRID_CAP sweep (workgroups of the iteration's streaming kernels) on the GPU box: tools/cap_sweep.sh "C4" 640 768 896 1024
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
 CFGS=$1; shift
-L="--no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
+L="--full --no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
 for C in $CFGS; do
   for R in 1 2; do
     for V in "$@"; do

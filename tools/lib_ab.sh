@@ -2,7 +2,7 @@
 # A/B of variant libraries on the GPU box: tools/lib_ab.sh "C3 C4" default libfluid_amd/variants/x.so ...   (each twice, interleaved)
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
 CFGS=$1; shift
-L="--no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
+L="--full --no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
 for C in $CFGS; do
   for R in 1 2; do
     for V in "$@"; do

@@ -3,6 +3,7 @@
 # the two HBM PMC passes; everything lands under gpurun_out/ (copy what is to be judged into profiles/).
 # usage: tools/make_profiles.sh TAG [bench args...]
 TAG=${1:-r04_c4}; shift
+set -- --full "$@"  # the bench line with every secondary figure; the traced runs below switch them off again (LIGHT)
 cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp; mkdir -p gpurun_out
 python3 bench.py "$@" > gpurun_out/${TAG}_bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
 # Per-kernel tables are taken with the stages of a step back to back (--no-overlap): in the default step the position correction

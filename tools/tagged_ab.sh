@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on the GPU box: k_mg_coarse's tagged hand-off (default, fp32) against the ready-flag form (LFA_MG_NO_TAGGED=1): PCG loop per config.
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
-L="--no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
+L="--full --no-cpu-baseline --no-hot-path --no-mic0-record --no-kernel-timing"
 for C in C2 C3 C4; do
   for V in top notop flags top notop flags; do
     unset LFA_MG_NO_TAGGED LFA_MG_NO_TOP
