@@ -362,6 +362,24 @@ int lfa_mesher_download_values(lfa_mesher *m, double *values);
 int lfa_mesher_upload_values(lfa_mesher *m, const double *values);
 int lfa_mesher_marching_cubes(lfa_mesher *m, uint64_t *n_vertices, uint64_t *n_indices);
 int lfa_mesher_download_mesh(lfa_mesher *m, double *positions, uint64_t *indices);
+/* Vertex normals of the mesh just extracted: mesh::generate_normals() (include/fluid/data_structures/mesh.h:38-53 with
+ * NormalT = double; cross product and normalized_checked of include/fluid/math/vec.h:355-398,546-548), which every caller runs
+ * right after generate_mesh (testbed/main.cpp:224-225). Bit-exact and reproducible: no atomics - every vertex gathers the face
+ * vectors of its triangles in ascending triangle index, the order of the reference's loop, which the vertex numbering gives
+ * without a sort (mesher.hip). A vertex whose sum is not longer than 1e-6 gets (1, 0, 0); a NaN sum stays NaN.
+ *   lfa_mesher_normals          : computes them on the device. LFA_E_INVALID unless lfa_mesher_marching_cubes has succeeded on
+ *                                 this handle since the values were last sampled or uploaded (never stale normals).
+ *                                 LFA_E_UNSUPPORTED on a z-window that is not the whole grid: the vertices on a window's upper
+ *                                 plane have triangles in the window above. An empty mesh is LFA_OK. Indices that
+ *                                 lfa_mesher_rebase has shifted give the same normals: the shift is remembered.
+ *   lfa_mesher_download_normals : double[3 nv] in the vertex order of lfa_mesher_download_mesh; LFA_E_INVALID without a preceding
+ *                                 lfa_mesher_normals for the current mesh; an empty mesh writes nothing.
+ *   lfa_mesher_normals_time     : device time of the last lfa_mesher_normals (HIP events on the mesher's stream, milliseconds)
+ * The buffers (24 B per vertex, 24 B per triangle) exist from the first lfa_mesher_normals on; a handle that never asks
+ * allocates and launches nothing more. */
+int lfa_mesher_normals(lfa_mesher *m);
+int lfa_mesher_download_normals(lfa_mesher *m, double *normals);
+int lfa_mesher_normals_time(lfa_mesher *m, double *ms);
 
 /* -- measurement --------------------------------------------------------------------------------------------- */
 /* Per-stage device time of the last lfa_step_hot, measured with HIP events on the handle's stream (milliseconds):

@@ -139,6 +139,9 @@ SIGNATURES = {
     "lfa_mesher_upload_values": (_int, [_vp, _vp]),
     "lfa_mesher_marching_cubes": (_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "lfa_mesher_download_mesh": (_int, [_vp, _vp, _vp]),
+    "lfa_mesher_normals": (_int, [_vp]),
+    "lfa_mesher_download_normals": (_int, [_vp, _vp]),
+    "lfa_mesher_normals_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_clear_sources": (_int, [_vp]),
     "lfa_add_source": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _int]),
     "lfa_update_sources": (_int, [_vp, C.POINTER(_u64)]),
@@ -385,9 +388,32 @@ class Mesher:
         self._chk(self.lib.lfa_mesher_download_mesh(self.h, _ptr(pos), _ptr(idx)))
         return pos, idx
 
-    def generate_mesh(self, points, r):
+    def compute_normals(self):
+        """lfa_mesher_normals: the normals of the mesh of the last marching_cubes(), kept on the device."""
+        self._chk(self.lib.lfa_mesher_normals(self.h))
+
+    def download_normals(self):
+        """float64[nv,3]: what compute_normals() left on the device, in the vertex order of download_mesh()."""
+        out = np.empty((getattr(self, "_counts", (0, 0))[0], 3), dtype=np.float64)
+        self._chk(self.lib.lfa_mesher_download_normals(self.h, _ptr(out)))
+        return out
+
+    def normals(self):
+        """mesh::generate_normals() of the mesh of the last marching_cubes(), bit for bit: float64[nv,3]."""
+        self.compute_normals()
+        return self.download_normals()
+
+    def normals_ms(self):
+        """Device time of the last compute_normals() (HIP events on the mesher's stream)."""
+        ms = _dbl()
+        self._chk(self.lib.lfa_mesher_normals_time(self.h, C.byref(ms)))
+        return ms.value
+
+    def generate_mesh(self, points, r, normals=False):
+        """(positions, indices), and the vertex normals behind them when `normals` is set."""
         self.sample(points, r)
-        return self.marching_cubes()
+        mesh = self.marching_cubes()
+        return (*mesh, self.normals()) if normals else mesh
 
     def close(self):
         if self.h:

@@ -55,6 +55,14 @@ struct lfa_mesher {
 	size_t vcap = 0, icap = 0;
 	uint64_t n_vertices = 0, n_indices = 0;
 	bool have_mesh = false;
+	// vertex normals (lfa_mesher_normals): nothing of this exists until the first request
+	double *face = nullptr;        // per triangle: the cross product of its two edges
+	double *vnorm = nullptr;       // per vertex
+	size_t fcap = 0, ncap = 0;
+	bool have_normals = false;
+	uint64_t rebased = 0;          // what lfa_mesher_rebase has added to the indices of the current mesh
+	hipEvent_t nrm_ev[2] = {nullptr, nullptr};
+	float normals_ms = 0.0f;
 	std::string err;
 };
 
@@ -386,6 +394,100 @@ k_mc_triangles(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const
 	}
 }
 
+// ------------------------------------------------------------------------------------------------ vertex normals
+// mesh::generate_normals (include/fluid/data_structures/mesh.h:38-53, NormalT = double): the face vectors are added to their
+// three corners in index-list order, then every sum is normalised. A vertex's bits depend on the order of its triangles, and
+// the numbering above gives that order without a sort: the cells that share the vertex's grid edge lie at offsets
+// (dx, dy, dz) in {0, 1}^3 from the cell that owns it (edge_owner only steps to -1), ascending (dz, dy, dx) is ascending
+// cell index, triangles are numbered by cell (ibase) and inside a cell by the row of the case table.
+// d_edge_in_neighbour[8 e + 4 dz + 2 dy + dx]: the number edge e of a cell has in the cell at that offset, MC_END where that
+// cell does not contain it (the inverse of edge_owner; filled at create time from the corner tables).
+__device__ uint8_t d_edge_in_neighbour[12 * 8];
+
+void edge_in_neighbour_table(uint8_t out[12 * 8]) {
+	for (int e = 0; e < 12; ++e)
+		for (int j = 0; j < 8; ++j) {
+			const int d[3] = {j & 1, (j >> 1) & 1, j >> 2};
+			int corner[2];
+			for (int s = 0; s < 2; ++s) {
+				corner[s] = -1;
+				for (int c = 0; c < 8; ++c) {
+					bool same = true;
+					for (int a = 0; a < 3; ++a) same = same && MC_CORNER_OFFSETS[c][a] + d[a] == MC_CORNER_OFFSETS[MC_EDGE_CORNERS[e][s]][a];
+					if (same) corner[s] = c;
+				}
+			}
+			out[8 * e + j] = MC_END;
+			for (int f = 0; f < 12; ++f)
+				if ((MC_EDGE_CORNERS[f][0] == corner[0] && MC_EDGE_CORNERS[f][1] == corner[1]) ||
+				    (MC_EDGE_CORNERS[f][0] == corner[1] && MC_EDGE_CORNERS[f][1] == corner[0]))
+					out[8 * e + j] = (uint8_t)f;
+		}
+}
+
+/// cross(p[i2] - p[i1], p[i3] - p[i1]) of every triangle (mesh.h:41-46, vec.h:546-548), one thread per triangle. `rebased`:
+/// what lfa_mesher_rebase has added to the index list since the extraction (the positions are stored from 0). An index that
+/// is not one of the nv vertices cannot come out of the extraction; it yields a NaN face vector rather than a read outside vpos.
+__global__ void __launch_bounds__(256)
+k_face_vectors(const double *vpos, const uint64_t *vidx, size_t nt, uint64_t rebased, uint64_t nv, double *face) {
+	const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= nt) return;
+	const uint64_t i1 = vidx[3 * t] - rebased, i2 = vidx[3 * t + 1] - rebased, i3 = vidx[3 * t + 2] - rebased;
+	if (i1 >= nv || i2 >= nv || i3 >= nv) {
+		face[3 * t] = face[3 * t + 1] = face[3 * t + 2] = __builtin_nan("");
+		return;
+	}
+	const double *p1 = vpos + 3 * i1, *p2 = vpos + 3 * i2, *p3 = vpos + 3 * i3;
+	const double ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
+	const double bx = p3[0] - p1[0], by = p3[1] - p1[1], bz = p3[2] - p1[2];
+	face[3 * t] = ay * bz - az * by;
+	face[3 * t + 1] = az * bx - ax * bz;
+	face[3 * t + 2] = ax * by - ay * bx;
+}
+
+/// The normal of every vertex a cell creates: its triangles' face vectors gathered in ascending triangle index (mesh.h:47-49),
+/// then normalized_checked or (1, 0, 0) (mesh.h:50-52, vec.h:377-399). One thread per cell; whole grid only (no z-window).
+__global__ void __launch_bounds__(256)
+k_vertex_normals(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const uint32_t *vbase, const uint32_t *ibase,
+                 const double *face, double *vnorm) {
+	const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= g.nx * g.ny * g.nzl) return;
+	const uint32_t mine = created[c];
+	if (!mine) return;
+	const uint64_t x = c % g.nx, y = (c / g.nx) % g.ny, z = c / (g.nx * g.ny);
+	const uint32_t vb = vbase[c];
+	for (int e = 0; e < 12; ++e) {
+		if (!(mine & (1u << e))) continue;
+		double sx = 0.0, sy = 0.0, sz = 0.0;
+		for (int j = 0; j < 8; ++j) {
+			const uint8_t ne = d_edge_in_neighbour[8 * e + j];
+			const uint64_t dx = j & 1, dy = (j >> 1) & 1, dz = j >> 2;
+			if (ne == MC_END || x + dx >= g.nx || y + dy >= g.ny || z + dz >= g.nzl) continue;
+			const size_t nc = c + dx + g.nx * (dy + g.ny * dz);
+			const uint8_t *row = d_tri_table + 16 * (size_t)occ_in[nc];
+			if (row[0] == MC_END) continue;
+			const double *f = face + ibase[nc];  // 3 doubles per triangle = 1 per index
+			for (int k = 0; k < 15 && row[k] != MC_END; k += 3) {
+				if (row[k] != ne && row[k + 1] != ne && row[k + 2] != ne) continue;
+				sx += f[k];
+				sy += f[k + 1];
+				sz += f[k + 2];
+			}
+		}
+		double sq = 0.0;  // vec_ops::dot
+		sq += sx * sx;
+		sq += sy * sy;
+		sq += sz * sz;
+		double *o = vnorm + 3 * ((size_t)vb + __popc(mine & before_mask(e)));
+		if (sq <= 1e-6 * 1e-6) {
+			o[0] = 1.0; o[1] = 0.0; o[2] = 0.0;
+		} else {  // (a NaN sum comes here too and stays NaN)
+			const double len = sqrt(sq);
+			o[0] = sx / len; o[1] = sy / len; o[2] = sz / len;
+		}
+	}
+}
+
 MeshGrid make_grid(const lfa_mesher *m) {
 	return MeshGrid{m->n[0], m->n[1], m->n[2], m->off[0], m->off[1], m->off[2], m->cs, m->extent, m->radius,
 	                m->z0, m->nzl, m->s_lo, m->s_hi, m->c_lo, m->c_hi, m->own_lo};
@@ -445,8 +547,11 @@ extern "C" int lfa_mesher_create_window(lfa_mesher **out, const uint64_t size[3]
 	          hipMalloc(&m->cell_fill, m->ncell * 4) == hipSuccess && hipMalloc(&m->vcount, (m->ncell + 1) * 4) == hipSuccess &&
 	          hipMalloc(&m->icount, (m->ncell + 1) * 4) == hipSuccess && hipMalloc(&m->created, m->ncell * 2) == hipSuccess &&
 	          hipMalloc(&m->occ, m->ncell) == hipSuccess && hipMalloc(&m->blk, (m->nblk + 1) * 4) == hipSuccess;
+	uint8_t nbr[12 * 8];
+	edge_in_neighbour_table(nbr);
 	// grid3<double>(size + 1): zero-initialised until the first sampling (src/mesher.cpp:321)
-	ok = ok && hipMemsetAsync(m->values, 0, m->npts * 8, m->stream) == hipSuccess &&
+	ok = ok && hipMemcpyToSymbolAsync(HIP_SYMBOL(d_edge_in_neighbour), nbr, sizeof nbr, 0, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
+	     hipMemsetAsync(m->values, 0, m->npts * 8, m->stream) == hipSuccess &&
 	     hipMemcpyToSymbolAsync(HIP_SYMBOL(d_tri_table), MC_TRIANGLES, 256 * 16, 0, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
 	     hipMemcpyToSymbolAsync(HIP_SYMBOL(d_edge_corners), MC_EDGE_CORNERS, 24, 0, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
 	     hipMemcpyToSymbolAsync(HIP_SYMBOL(d_corner_offsets), MC_CORNER_OFFSETS, 24, 0, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
@@ -479,9 +584,11 @@ extern "C" void lfa_mesher_destroy(lfa_mesher *m) {
 	(void)hipSetDevice(m->device);
 	if (m->stream) (void)hipStreamSynchronize(m->stream);
 	void *ptrs[] = {m->ids, m->values, m->cell_start, m->cell_fill, m->order, m->pos, m->spos, m->blk_flag, m->vcount, m->icount, m->created, m->occ, m->blk,
-	                m->vpos, m->vidx};
+	                m->vpos, m->vidx, m->face, m->vnorm};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
+	for (hipEvent_t e : m->nrm_ev)
+		if (e) (void)hipEventDestroy(e);
 	if (m->stream) (void)hipStreamDestroy(m->stream);
 	delete m;
 }
@@ -519,6 +626,7 @@ static int sample_device_positions(lfa_mesher *m, const double *dpos, uint64_t n
 	                   (const uint32_t *)m->cell_start, (const uint8_t *)m->blk_flag, r, m->values);
 	MSH_HIP(m, hipGetLastError());
 	m->have_mesh = false;
+	m->have_normals = false;
 	return LFA_OK;
 }
 
@@ -627,12 +735,16 @@ extern "C" int lfa_mesher_upload_values(lfa_mesher *m, const double *values) {
 	MSH_HIP(m, hipMemcpyAsync(m->values, values, m->npts * 8, hipMemcpyHostToDevice, m->stream));
 	MSH_HIP(m, hipStreamSynchronize(m->stream));
 	m->have_mesh = false;
+	m->have_normals = false;
 	return LFA_OK;
 }
 
 extern "C" int lfa_mesher_marching_cubes(lfa_mesher *m, uint64_t *n_vertices, uint64_t *n_indices) {
 	if (!m) return LFA_E_INVALID;
 	MSH_HIP(m, hipSetDevice(m->device));
+	m->have_mesh = false;  // until this extraction has succeeded: a failure half way leaves no mesh, not a mix of two
+	m->have_normals = false;
+	m->rebased = 0;
 	const MeshGrid g = make_grid(m);
 	const unsigned grid = (unsigned)((m->ncell + 255) / 256);
 	hipLaunchKernelGGL(k_mc_classify, dim3(grid), dim3(256), 0, m->stream, g, (const double *)m->values, m->occ, m->created,
@@ -687,6 +799,7 @@ extern "C" int lfa_mesher_rebase(lfa_mesher *m, uint64_t vertices_below) {
 		                   (int64_t)vertices_below);
 		MSH_HIP(m, hipGetLastError());
 		MSH_HIP(m, hipStreamSynchronize(m->stream));
+		m->rebased += vertices_below;
 	}
 	return LFA_OK;
 }
@@ -700,5 +813,66 @@ extern "C" int lfa_mesher_download_mesh(lfa_mesher *m, double *positions, uint64
 	if (indices && m->n_indices)
 		MSH_HIP(m, hipMemcpyAsync(indices, m->vidx, (size_t)m->n_indices * 8, hipMemcpyDeviceToHost, m->stream));
 	MSH_HIP(m, hipStreamSynchronize(m->stream));
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_normals(lfa_mesher *m) {
+	if (!m) return LFA_E_INVALID;
+	if (m->own_lo != 0 || m->c_hi != m->n[2])
+		return mfail(m, LFA_E_UNSUPPORTED, "lfa_mesher_normals: a z-window does not hold every triangle of the vertices on its upper plane; "
+		                                    "normals need the whole grid on one handle");
+	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, "lfa_mesher_normals: no current mesh, call lfa_mesher_marching_cubes first");
+	MSH_HIP(m, hipSetDevice(m->device));
+	const size_t nv = (size_t)m->n_vertices, nt = (size_t)(m->n_indices / 3);
+	m->normals_ms = 0.0f;
+	if (nv && nt) {
+		if (nv > m->ncap) {
+			if (m->vnorm) MSH_HIP(m, hipFree(m->vnorm));
+			m->vnorm = nullptr;
+			m->ncap = 0;
+			MSH_HIP(m, hipMalloc(&m->vnorm, nv * 24));
+			m->ncap = nv;
+		}
+		if (nt > m->fcap) {
+			if (m->face) MSH_HIP(m, hipFree(m->face));
+			m->face = nullptr;
+			m->fcap = 0;
+			MSH_HIP(m, hipMalloc(&m->face, nt * 24));
+			m->fcap = nt;
+		}
+		for (hipEvent_t &e : m->nrm_ev)
+			if (!e) MSH_HIP(m, hipEventCreate(&e));
+		MSH_HIP(m, hipEventRecord(m->nrm_ev[0], m->stream));
+		hipLaunchKernelGGL(k_face_vectors, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, m->stream, (const double *)m->vpos,
+		                   (const uint64_t *)m->vidx, nt, m->rebased, (uint64_t)nv, m->face);
+		hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((m->ncell + 255) / 256)), dim3(256), 0, m->stream, make_grid(m),
+		                   (const uint8_t *)m->occ, (const uint16_t *)m->created, (const uint32_t *)m->vcount,
+		                   (const uint32_t *)m->icount, (const double *)m->face, m->vnorm);
+		MSH_HIP(m, hipGetLastError());
+		MSH_HIP(m, hipEventRecord(m->nrm_ev[1], m->stream));
+		MSH_HIP(m, hipStreamSynchronize(m->stream));
+		MSH_HIP(m, hipEventElapsedTime(&m->normals_ms, m->nrm_ev[0], m->nrm_ev[1]));
+	}
+	m->have_normals = true;
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_normals_time(lfa_mesher *m, double *ms) {
+	if (!m || !ms) return LFA_E_INVALID;
+	if (!m->have_mesh || !m->have_normals)
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_normals_time: call lfa_mesher_normals for the current mesh first");
+	*ms = (double)m->normals_ms;
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_download_normals(lfa_mesher *m, double *normals) {
+	if (!m) return LFA_E_INVALID;
+	if (!m->have_mesh || !m->have_normals)
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_download_normals: call lfa_mesher_normals for the current mesh first");
+	MSH_HIP(m, hipSetDevice(m->device));
+	if (normals && m->n_vertices && m->n_indices >= 3) {
+		MSH_HIP(m, hipMemcpyAsync(normals, m->vnorm, (size_t)m->n_vertices * 24, hipMemcpyDeviceToHost, m->stream));
+		MSH_HIP(m, hipStreamSynchronize(m->stream));
+	}
 	return LFA_OK;
 }

@@ -2,8 +2,10 @@
 // (include/fluid/mesher.h:14-46): resize(vec3s), generate_mesh(particles, r), and the public fields grid_offset, cell_size,
 // particle_extent, cell_radius. Sampling of the surface function and marching cubes run on an MI355X through the C ABI
 // (include/libfluid_amd.h, lfa_mesher_*); the mesh comes back as fluid_amd::mesh (host/mesh.h) with positions and
-// indices only, like the reference's. Header-only; link with libfluid_amd.so. Bit-exact with the reference
-// (tests/test_mesher.py, tests/test_host_mesher.py). Never throws; device errors are kept in last_status()/last_error().
+// indices only, like the reference's; generate_mesh_with_normals also fills `normals` on the device, with the bits of
+// mesh::generate_normals(). Header-only; link with libfluid_amd.so. Bit-exact with the reference (tests/test_mesher.py,
+// tests/test_host_mesher.py, tests/test_host_mesher_normals.py). Never throws; device errors are kept in
+// last_status()/last_error().
 #pragma once
 
 #include <string>
@@ -42,6 +44,21 @@ namespace fluid_amd {
 			if (!_ensure() || !sim.device_handle()) return out;
 			_status = lfa_mesher_sample_sim(_dev, sim.device_handle(), r);
 			return _status == LFA_OK ? _extract() : (_error = lfa_mesher_last_error(_dev), out);
+		}
+
+		/// generate_mesh followed by mesh_t::generate_normals() (testbed/main.cpp:224-225) in one call: the normals are computed on
+		/// the device from the mesh it still holds and equal the host loop's bit for bit (normals.size() == positions.size()).
+		[[nodiscard]] mesh_t generate_mesh_with_normals(const std::vector<vec3d> &particles, double r) {
+			mesh_t out;
+			if (!_ensure()) return out;
+			_status = lfa_mesher_sample(_dev, reinterpret_cast<const double *>(particles.data()), particles.size(), r);
+			return _status == LFA_OK ? _extract(true) : (_error = lfa_mesher_last_error(_dev), out);
+		}
+		[[nodiscard]] mesh_t generate_mesh_with_normals(simulation &sim, double r) {
+			mesh_t out;
+			if (!_ensure() || !sim.device_handle()) return out;
+			_status = lfa_mesher_sample_sim(_dev, sim.device_handle(), r);
+			return _status == LFA_OK ? _extract(true) : (_error = lfa_mesher_last_error(_dev), out);
 		}
 
 		vec3d grid_offset;
@@ -84,7 +101,7 @@ namespace fluid_amd {
 			_dev_radius = cell_radius;
 			return true;
 		}
-		mesh_t _extract() {
+		mesh_t _extract(bool with_normals = false) {
 			mesh_t out;
 			std::uint64_t nv = 0, ni = 0;
 			_status = lfa_mesher_marching_cubes(_dev, &nv, &ni);
@@ -97,6 +114,16 @@ namespace fluid_amd {
 			_status = lfa_mesher_download_mesh(_dev, reinterpret_cast<double *>(out.positions.data()), idx.data());
 			if (_status != LFA_OK) _error = lfa_mesher_last_error(_dev);
 			out.indices.assign(idx.begin(), idx.end());
+			if (with_normals && _status == LFA_OK) {
+				static_assert(sizeof(out.normals[0]) == 24, "mesh_t::normals must be three packed doubles");
+				out.normals.resize(nv);
+				_status = lfa_mesher_normals(_dev);
+				if (_status == LFA_OK) _status = lfa_mesher_download_normals(_dev, reinterpret_cast<double *>(out.normals.data()));
+				if (_status != LFA_OK) {
+					_error = lfa_mesher_last_error(_dev);
+					out.normals.clear();
+				}
+			}
 			return out;
 		}
 	};
