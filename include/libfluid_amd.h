@@ -380,6 +380,35 @@ int lfa_mesher_download_mesh(lfa_mesher *m, double *positions, uint64_t *indices
 int lfa_mesher_normals(lfa_mesher *m);
 int lfa_mesher_download_normals(lfa_mesher *m, double *normals);
 int lfa_mesher_normals_time(lfa_mesher *m, double *ms);
+/* The same on z-windows, for a slab run: what replaces downloading every rank's mesh, concatenating them and running the serial
+ * mesh::generate_normals() (mesh.h:38-53) on the host. The windows' normals, concatenated in z order, are the single grid's bit
+ * for bit. A vertex on a window's upper plane has triangles in the first cell layer of the window above; they are the last
+ * terms of its ordered sum, so the lower window continues its sum with that layer's face vectors. These, with the layer's case
+ * bytes, are the upper window's BOUNDARY: uint8 case per cell of its layer own_lo (nx ny, x fastest) and double[3] per triangle of
+ * that layer in triangle order (a prefix of its triangle list). The caller moves it to the window below; the windows need nothing
+ * else from each other (the vertices of the plane below a window are recomputed from its own samples, mesher.cpp:378-392).
+ *   lfa_mesher_boundary_size       : cells (nx ny) and triangles of the boundary of the current mesh. LFA_E_INVALID without a
+ *                                    current mesh or on a window that starts at layer 0.
+ *   lfa_mesher_download_boundary   : the boundary into host memory (cases[n_cells], face[3 n_triangles]); the face vectors are
+ *                                    computed on the first request for the current mesh.
+ *   lfa_mesher_window_normals      : mesh::generate_normals() for the vertices this window owns, kept on the device for
+ *                                    lfa_mesher_download_normals / lfa_mesher_normals_time. cases_above / face_above /
+ *                                    n_triangles_above: the boundary of the window directly above; NULL / NULL / 0 exactly when the
+ *                                    window reaches the top of the grid (on the whole grid this is lfa_mesher_normals).
+ *                                    LFA_E_INVALID, and no normals, when a boundary is missing or surplus, when n_triangles_above
+ *                                    is not what cases_above imply, or when the boundary contradicts this window's mesh: the
+ *                                    bottom corners of every imported cell are the top corners of the own cell below it and must
+ *                                    lie on the same side of the surface (a stale boundary, or one of another window; the message
+ *                                    names the first such cell).
+ *   lfa_mesher_window_normals_from : the same with the boundary taken from the handle of the window directly above (same grid,
+ *                                    above->own_lo == own_hi, else LFA_E_INVALID): device to device on one GPU, staged through the
+ *                                    host otherwise.
+ * lfa_mesher_rebase on either handle, before or after, changes nothing. Normals and boundary go stale like lfa_mesher_normals'
+ * results. The buffers (boundary in and out, the recomputed vertices) exist from the first request on. */
+int lfa_mesher_boundary_size(lfa_mesher *m, uint64_t *n_cells, uint64_t *n_triangles);
+int lfa_mesher_download_boundary(lfa_mesher *m, uint8_t *cases, double *face);
+int lfa_mesher_window_normals(lfa_mesher *m, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above);
+int lfa_mesher_window_normals_from(lfa_mesher *m, lfa_mesher *above);
 
 /* -- measurement --------------------------------------------------------------------------------------------- */
 /* Per-stage device time of the last lfa_step_hot, measured with HIP events on the handle's stream (milliseconds):

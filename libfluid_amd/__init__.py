@@ -142,6 +142,10 @@ SIGNATURES = {
     "lfa_mesher_normals": (_int, [_vp]),
     "lfa_mesher_download_normals": (_int, [_vp, _vp]),
     "lfa_mesher_normals_time": (_int, [_vp, C.POINTER(_dbl)]),
+    "lfa_mesher_boundary_size": (_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "lfa_mesher_download_boundary": (_int, [_vp, _vp, _vp]),
+    "lfa_mesher_window_normals": (_int, [_vp, _vp, _vp, _u64]),
+    "lfa_mesher_window_normals_from": (_int, [_vp, _vp]),
     "lfa_clear_sources": (_int, [_vp]),
     "lfa_add_source": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _int]),
     "lfa_update_sources": (_int, [_vp, C.POINTER(_u64)]),
@@ -331,6 +335,9 @@ class Mesher:
         """window = (zlo, zhi): only the cell layers [zlo, zhi) of the grid (lfa_mesher_create_window)."""
         self.lib = load_library()
         self.size = tuple(int(x) for x in size)
+        # (what a window of the same grid is created with)
+        self.grid = dict(grid_offset=tuple(float(x) for x in grid_offset), cell_size=float(cell_size),
+                         particle_extent=float(particle_extent), cell_radius=int(cell_radius))
         sz, off = np.asarray(self.size, dtype=np.uint64), np.asarray(grid_offset, dtype=np.float64)
         h = C.c_void_p()
         zlo, zhi = (0, self.size[2]) if window is None else window
@@ -374,6 +381,12 @@ class Mesher:
         assert v.size == (self.size[0] + 1) * (self.size[1] + 1) * (self.size[2] + 1)
         self._chk(self.lib.lfa_mesher_upload_values(self.h, _ptr(v)))
 
+    def set_window_values(self, full_field):
+        """Uploads the stored planes [z0, z0 + n_planes) of a whole-grid field float64[nz+1, ny+1, nx+1]."""
+        v = np.asarray(full_field, dtype=np.float64).reshape(self.size[2] + 1, self.size[1] + 1, self.size[0] + 1)
+        v = np.ascontiguousarray(v[self.z0:self.z0 + self.n_planes])
+        self._chk(self.lib.lfa_mesher_upload_values(self.h, _ptr(v)))
+
     def marching_cubes(self):
         """(positions float64[nv,3], indices uint64[ni])"""
         nv, ni = _u64(), _u64()
@@ -409,6 +422,35 @@ class Mesher:
         self._chk(self.lib.lfa_mesher_normals_time(self.h, C.byref(ms)))
         return ms.value
 
+    def boundary(self):
+        """lfa_mesher_download_boundary: (cases uint8[ny, nx], face float64[nt, 3]) of the first own cell layer, what the window
+        below needs for its normals."""
+        nc, nt = _u64(), _u64()
+        self._chk(self.lib.lfa_mesher_boundary_size(self.h, C.byref(nc), C.byref(nt)))
+        cases, face = np.empty((self.size[1], self.size[0]), dtype=np.uint8), np.empty((nt.value, 3), dtype=np.float64)
+        assert cases.size == nc.value
+        self._chk(self.lib.lfa_mesher_download_boundary(self.h, _ptr(cases), _ptr(face)))
+        return cases, face
+
+    def compute_window_normals(self, above=None):
+        """lfa_mesher_window_normals(_from): `above` is the Mesher of the window directly above or the pair of its boundary();
+        None on a window that reaches the top of the grid."""
+        if isinstance(above, Mesher):
+            self._chk(self.lib.lfa_mesher_window_normals_from(self.h, above.h))
+        elif above is None:
+            self._chk(self.lib.lfa_mesher_window_normals(self.h, None, None, 0))
+        else:
+            cases, face = above
+            cases = np.ascontiguousarray(cases, dtype=np.uint8)
+            face = np.ascontiguousarray(face, dtype=np.float64).reshape(-1, 3)
+            assert cases.size == self.size[0] * self.size[1]
+            self._chk(self.lib.lfa_mesher_window_normals(self.h, _ptr(cases), _ptr(face), face.shape[0]))
+
+    def window_normals(self, above=None):
+        """The normals of the vertices this window owns, float64[nv,3]: the rows of mesh::generate_normals() of the whole grid."""
+        self.compute_window_normals(above)
+        return self.download_normals()
+
     def generate_mesh(self, points, r, normals=False):
         """(positions, indices), and the vertex normals behind them when `normals` is set."""
         self.sample(points, r)
@@ -425,6 +467,22 @@ class Mesher:
             self.close()
         except Exception:
             pass
+
+
+def stitch_windows(meshers, normals=False):
+    """The mesh of one grid from its z-windows: `meshers` in ascending z, each with a current mesh. Rebases every window by the
+    exclusive scan of the vertex counts, hands the boundaries down when `normals` is set, and returns the concatenated
+    (positions, indices[, normals])."""
+    below, pos, idx, nrm = 0, [], [], []
+    for k, m in enumerate(meshers):
+        m.rebase(below)
+        p, i = m.download_mesh()
+        pos.append(p); idx.append(i)
+        below += len(p)
+        if normals:
+            nrm.append(m.window_normals(meshers[k + 1] if k + 1 < len(meshers) else None))
+    out = (np.concatenate(pos), np.concatenate(idx))
+    return (*out, np.concatenate(nrm)) if normals else out
 
 
 def default_params():

@@ -19,6 +19,7 @@
 #include "mc_tables.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -63,6 +64,15 @@ struct lfa_mesher {
 	uint64_t rebased = 0;          // what lfa_mesher_rebase has added to the indices of the current mesh
 	hipEvent_t nrm_ev[2] = {nullptr, nullptr};
 	float normals_ms = 0.0f;
+	// normals on a z-window (lfa_mesher_window_normals, lfa_mesher_download_boundary): nothing of this exists until the first request
+	uint32_t vsub = 0;             // vertices the cells of layer own_lo - 1 create (numbered here, stored by the window below)
+	double *vbelow = nullptr;      // their positions, recomputed from the planes own_lo - 1 .. own_lo: 3 vsub
+	size_t bvcap = 0;
+	bool have_face = false;        // `face` holds the face vectors of the current mesh (the first layer's are the boundary)
+	uint8_t *b_cases = nullptr;    // imported boundary: case bytes of layer c_hi (nx ny), their index offsets (nx ny + 1),
+	uint32_t *b_off = nullptr, *b_flag = nullptr;  // the first cell that contradicts the own layer below it
+	double *b_face = nullptr;      // and that layer's face vectors
+	size_t bfcap = 0;
 	std::string err;
 };
 
@@ -349,7 +359,26 @@ k_mc_classify(MeshGrid g, const double *values, uint8_t *occ_out, uint16_t *crea
 	icount[c] = (uint32_t)ni;
 }
 
-/// mesher::_add_point (src/mesher.cpp:378-392) for every vertex a cell creates, at its index in the sweep's numbering.
+/// mesher::_add_point (src/mesher.cpp:378-392) for every vertex cell c = (x, y, z) creates: vertex k of the cell goes to out + 3 k.
+__device__ inline void cell_vertices(const MeshGrid &g, const double *values, uint32_t mine, uint64_t x, uint64_t y, uint64_t z,
+                                     double *out) {
+	double f[8];
+	cell_case(g, values, x, y, z, f);
+	const double cell[3] = {(double)x, (double)y, (double)z}, off[3] = {g.ox, g.oy, g.oz};
+	for (int e = 0; e < 12; ++e) {
+		if (!(mine & (1u << e))) continue;
+		const int a = d_edge_corners[2 * e], b = d_edge_corners[2 * e + 1];
+		const double v1 = f[a], v2 = f[b], t = v1 / (v1 - v2);
+		double *o = out + 3 * (size_t)__popc(mine & before_mask(e));
+#pragma unroll
+		for (int d = 0; d < 3; ++d) {
+			// vec3d(cell + offset): integer sum converted to double; lerp(a, b, t) = a (1 - t) + b t (misc.h:20-22)
+			const double pa = cell[d] + (double)d_corner_offsets[3 * a + d], pb = cell[d] + (double)d_corner_offsets[3 * b + d];
+			o[d] = off[d] + g.cs * (pa * (1.0 - t) + pb * t);
+		}
+	}
+}
+/// The vertices of the own layers, at their index in the sweep's numbering.
 __global__ void __launch_bounds__(256)
 k_mc_vertices(MeshGrid g, const double *values, const uint16_t *created, const uint32_t *vbase, double *vpos, uint32_t vsub) {
 	const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -358,21 +387,19 @@ k_mc_vertices(MeshGrid g, const double *values, const uint16_t *created, const u
 	if (!mine) return;
 	const uint64_t x = c % g.nx, y = (c / g.nx) % g.ny, z = g.z0 + c / (g.nx * g.ny);
 	if (z < g.own_lo) return;  // numbered here, created by the rank below
-	double f[8];
-	cell_case(g, values, x, y, z, f);
-	const double cell[3] = {(double)x, (double)y, (double)z}, off[3] = {g.ox, g.oy, g.oz};
-	for (int e = 0; e < 12; ++e) {
-		if (!(mine & (1u << e))) continue;
-		const int a = d_edge_corners[2 * e], b = d_edge_corners[2 * e + 1];
-		const double v1 = f[a], v2 = f[b], t = v1 / (v1 - v2);
-		double *o = vpos + 3 * ((size_t)(vbase[c] - vsub) + __popc(mine & before_mask(e)));
-#pragma unroll
-		for (int d = 0; d < 3; ++d) {
-			// vec3d(cell + offset): integer sum converted to double; lerp(a, b, t) = a (1 - t) + b t (misc.h:20-22)
-			const double pa = cell[d] + (double)d_corner_offsets[3 * a + d], pb = cell[d] + (double)d_corner_offsets[3 * b + d];
-			o[d] = off[d] + g.cs * (pa * (1.0 - t) + pb * t);
-		}
-	}
+	cell_vertices(g, values, mine, x, y, z, vpos + 3 * (size_t)(vbase[c] - vsub));
+}
+/// The vertices of layer own_lo - 1, which the window below stores: the same arithmetic on the same samples (the planes
+/// own_lo - 1 and own_lo are sampled here too), so the same bits, without asking the rank below. vbelow holds vbase[first own
+/// cell] of them; a triangle of layer own_lo refers to them with the relative indices [-vsub, 0). One thread per cell of the layer.
+__global__ void __launch_bounds__(256)
+k_mc_vertices_below(MeshGrid g, const double *values, const uint16_t *created, const uint32_t *vbase, double *vbelow) {
+	const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= g.nx * g.ny || g.own_lo == 0) return;
+	const size_t c = k + (size_t)(g.nx * g.ny * (g.own_lo - 1 - g.z0));
+	const uint32_t mine = created[c];
+	if (!mine) return;
+	cell_vertices(g, values, mine, k % g.nx, k / g.nx, g.own_lo - 1, vbelow + 3 * (size_t)vbase[c]);
 }
 
 __global__ void __launch_bounds__(256)
@@ -467,6 +494,104 @@ k_vertex_normals(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, con
 			const uint8_t *row = d_tri_table + 16 * (size_t)occ_in[nc];
 			if (row[0] == MC_END) continue;
 			const double *f = face + ibase[nc];  // 3 doubles per triangle = 1 per index
+			for (int k = 0; k < 15 && row[k] != MC_END; k += 3) {
+				if (row[k] != ne && row[k + 1] != ne && row[k + 2] != ne) continue;
+				sx += f[k];
+				sy += f[k + 1];
+				sz += f[k + 2];
+			}
+		}
+		double sq = 0.0;  // vec_ops::dot
+		sq += sx * sx;
+		sq += sy * sy;
+		sq += sz * sz;
+		double *o = vnorm + 3 * ((size_t)vb + __popc(mine & before_mask(e)));
+		if (sq <= 1e-6 * 1e-6) {
+			o[0] = 1.0; o[1] = 0.0; o[2] = 0.0;
+		} else {  // (a NaN sum comes here too and stays NaN)
+			const double len = sqrt(sq);
+			o[0] = sx / len; o[1] = sy / len; o[2] = sz / len;
+		}
+	}
+}
+
+// ---- the same on a z-window (lfa_mesher_window_normals). Two things differ from the whole grid. The triangles of the first own
+// layer refer to vertices of the plane own_lo, which the window below stores: k_mc_vertices_below recomputes them. And the
+// vertices on the plane c_hi have triangles in layer c_hi, the first layer of the window above; they come last in such a
+// vertex's ordered sum (z is the slowest axis of the triangle numbering), so the sum is simply continued with that layer's face
+// vectors, which the window above exports (its "boundary": case bytes and face vectors of its layer own_lo, a prefix of its
+// triangle list).
+
+/// k_face_vectors on a window: a relative index in [-vsub, 0) is a vertex of the layer below and reads vbelow.
+__global__ void __launch_bounds__(256)
+k_window_face_vectors(const double *vpos, const double *vbelow, const uint64_t *vidx, size_t nt, uint64_t rebased, uint64_t nv,
+                      uint64_t vsub, double *face) {
+	const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= nt) return;
+	const double *p[3];
+	for (int k = 0; k < 3; ++k) {
+		const uint64_t i = vidx[3 * t + k] - rebased, b = i + vsub;  // (two's complement: b < vsub for i in [-vsub, 0))
+		if (i < nv) p[k] = vpos + 3 * i;
+		else if (b < vsub) p[k] = vbelow + 3 * b;
+		else {
+			face[3 * t] = face[3 * t + 1] = face[3 * t + 2] = __builtin_nan("");
+			return;
+		}
+	}
+	const double *p1 = p[0], *p2 = p[1], *p3 = p[2];
+	const double ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
+	const double bx = p3[0] - p1[0], by = p3[1] - p1[1], bz = p3[2] - p1[2];
+	face[3 * t] = ay * bz - az * by;
+	face[3 * t + 1] = az * bx - ax * bz;
+	face[3 * t + 2] = ax * by - ay * bx;
+}
+
+/// Set-up of an imported boundary, one thread per cell of layer c_hi: the number of indices of its case (scanned into offsets
+/// into b_face afterwards), and the consistency check: the cell's four bottom corners are the four top corners of the own cell
+/// below it (corner i + 4 lies above corner i, mc_tables.h), so their sign bits must agree. flag: the lowest offending cell.
+__global__ void __launch_bounds__(256)
+k_boundary_setup(MeshGrid g, const uint8_t *occ_in, const uint8_t *b_cases, uint32_t *b_count, uint32_t *flag) {
+	const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= g.nx * g.ny) return;
+	const uint8_t above = b_cases[k], own = occ_in[k + (size_t)(g.nx * g.ny * (g.c_hi - 1 - g.z0))];
+	int ni = 0;
+	while (ni < 16 && d_tri_table[above * 16 + ni] != MC_END) ++ni;
+	b_count[k] = (uint32_t)ni;
+	if ((above & 0xF) != (own >> 4)) atomicMin(flag, (uint32_t)k);
+}
+
+/// k_vertex_normals on a window: one thread per cell of the own layers [own_lo, c_hi) (the cells of layer own_lo - 1 are
+/// numbered here but belong to the window below); vertex slots are vbase - vsub. A neighbour in layer c_hi < nz is read from the
+/// imported boundary (locally that layer is classified as empty). Without a layer above (c_hi == nz) b_* are not read.
+__global__ void __launch_bounds__(256)
+k_window_vertex_normals(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const uint32_t *vbase, const uint32_t *ibase,
+                        const double *face, uint32_t vsub, const uint8_t *b_cases, const uint32_t *b_off, const double *b_face,
+                        double *vnorm) {
+	const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= g.nx * g.ny * g.nzl) return;
+	const uint32_t mine = created[c];
+	if (!mine) return;
+	const uint64_t x = c % g.nx, y = (c / g.nx) % g.ny, z = g.z0 + c / (g.nx * g.ny);
+	if (z < g.own_lo || z >= g.c_hi) return;
+	const uint32_t vb = vbase[c] - vsub;
+	for (int e = 0; e < 12; ++e) {
+		if (!(mine & (1u << e))) continue;
+		double sx = 0.0, sy = 0.0, sz = 0.0;
+		for (int j = 0; j < 8; ++j) {
+			const uint8_t ne = d_edge_in_neighbour[8 * e + j];
+			const uint64_t dx = j & 1, dy = (j >> 1) & 1, dz = j >> 2;
+			if (ne == MC_END || x + dx >= g.nx || y + dy >= g.ny || z + dz >= g.nz) continue;
+			const uint8_t *row;
+			const double *f;  // 3 doubles per triangle = 1 per index
+			if (z + dz == g.c_hi) {
+				const size_t bc = (size_t)((x + dx) + g.nx * (y + dy));
+				row = d_tri_table + 16 * (size_t)b_cases[bc];
+				f = b_face + b_off[bc];
+			} else {
+				const size_t nc = c + dx + g.nx * (dy + g.ny * dz);
+				row = d_tri_table + 16 * (size_t)occ_in[nc];
+				f = face + ibase[nc];
+			}
 			for (int k = 0; k < 15 && row[k] != MC_END; k += 3) {
 				if (row[k] != ne && row[k + 1] != ne && row[k + 2] != ne) continue;
 				sx += f[k];
@@ -584,7 +709,7 @@ extern "C" void lfa_mesher_destroy(lfa_mesher *m) {
 	(void)hipSetDevice(m->device);
 	if (m->stream) (void)hipStreamSynchronize(m->stream);
 	void *ptrs[] = {m->ids, m->values, m->cell_start, m->cell_fill, m->order, m->pos, m->spos, m->blk_flag, m->vcount, m->icount, m->created, m->occ, m->blk,
-	                m->vpos, m->vidx, m->face, m->vnorm};
+	                m->vpos, m->vidx, m->face, m->vnorm, m->vbelow, m->b_cases, m->b_off, m->b_flag, m->b_face};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	for (hipEvent_t e : m->nrm_ev)
@@ -627,6 +752,7 @@ static int sample_device_positions(lfa_mesher *m, const double *dpos, uint64_t n
 	MSH_HIP(m, hipGetLastError());
 	m->have_mesh = false;
 	m->have_normals = false;
+	m->have_face = false;
 	return LFA_OK;
 }
 
@@ -736,6 +862,7 @@ extern "C" int lfa_mesher_upload_values(lfa_mesher *m, const double *values) {
 	MSH_HIP(m, hipStreamSynchronize(m->stream));
 	m->have_mesh = false;
 	m->have_normals = false;
+	m->have_face = false;
 	return LFA_OK;
 }
 
@@ -744,6 +871,7 @@ extern "C" int lfa_mesher_marching_cubes(lfa_mesher *m, uint64_t *n_vertices, ui
 	MSH_HIP(m, hipSetDevice(m->device));
 	m->have_mesh = false;  // until this extraction has succeeded: a failure half way leaves no mesh, not a mix of two
 	m->have_normals = false;
+	m->have_face = false;
 	m->rebased = 0;
 	const MeshGrid g = make_grid(m);
 	const unsigned grid = (unsigned)((m->ncell + 255) / 256);
@@ -760,6 +888,7 @@ extern "C" int lfa_mesher_marching_cubes(lfa_mesher *m, uint64_t *n_vertices, ui
 	MSH_HIP(m, hipMemcpyAsync(&tot[2], m->vcount + first_own, 4, hipMemcpyDeviceToHost, m->stream));  // vertices of the layer below
 	MSH_HIP(m, hipStreamSynchronize(m->stream));
 	const uint32_t vsub = tot[2], nv = tot[0] - tot[2];
+	m->vsub = vsub;
 	if (nv > m->vcap) {
 		if (m->vpos) MSH_HIP(m, hipFree(m->vpos));
 		m->vpos = nullptr;
@@ -875,4 +1004,176 @@ extern "C" int lfa_mesher_download_normals(lfa_mesher *m, double *normals) {
 		MSH_HIP(m, hipStreamSynchronize(m->stream));
 	}
 	return LFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ normals on a z-window
+/// (Re)allocates *p for `need` elements of `elem` bytes when the capacity is smaller.
+template <typename T> static int grow(lfa_mesher *m, T **p, size_t *cap, size_t need, size_t elem) {
+	if (need <= *cap) return LFA_OK;
+	if (*p) MSH_HIP(m, hipFree(*p));
+	*p = nullptr;
+	*cap = 0;
+	MSH_HIP(m, hipMalloc(p, need * elem));
+	*cap = need;
+	return LFA_OK;
+}
+
+/// The face vectors of the current mesh into m->face (launched on the stream, not waited for), unless they are there already.
+static int ensure_face(lfa_mesher *m) {
+	const size_t nt = (size_t)(m->n_indices / 3);
+	if (m->have_face || !nt) return LFA_OK;
+	int rc = grow(m, &m->face, &m->fcap, nt, 24);
+	if (rc == LFA_OK && m->vsub) rc = grow(m, &m->vbelow, &m->bvcap, (size_t)m->vsub, 24);
+	if (rc != LFA_OK) return rc;
+	if (m->vsub)
+		hipLaunchKernelGGL(k_mc_vertices_below, dim3((unsigned)((m->n[0] * m->n[1] + 255) / 256)), dim3(256), 0, m->stream, make_grid(m),
+		                   (const double *)m->values, (const uint16_t *)m->created, (const uint32_t *)m->vcount, m->vbelow);
+	hipLaunchKernelGGL(k_window_face_vectors, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, m->stream, (const double *)m->vpos,
+	                   (const double *)m->vbelow, (const uint64_t *)m->vidx, nt, m->rebased, m->n_vertices, (uint64_t)m->vsub, m->face);
+	MSH_HIP(m, hipGetLastError());
+	m->have_face = true;
+	return LFA_OK;
+}
+
+/// Triangles of the first own layer: the triangle list starts with them (the layer below emits none), so their number is the
+/// index offset of the first cell of the layer after it.
+static int boundary_triangles(lfa_mesher *m, const char *who, uint64_t *nt) {
+	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, (std::string(who) + ": no current mesh, call lfa_mesher_marching_cubes first").c_str());
+	if (m->own_lo == 0) return mfail(m, LFA_E_INVALID, (std::string(who) + ": the window starts at layer 0, nothing lies below it").c_str());
+	uint32_t ni = 0;
+	MSH_HIP(m, hipMemcpyAsync(&ni, m->icount + (size_t)m->n[0] * m->n[1] * (m->own_lo + 1 - m->z0), 4, hipMemcpyDeviceToHost, m->stream));
+	MSH_HIP(m, hipStreamSynchronize(m->stream));
+	*nt = ni / 3;
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_boundary_size(lfa_mesher *m, uint64_t *n_cells, uint64_t *n_triangles) {
+	if (!m) return LFA_E_INVALID;
+	MSH_HIP(m, hipSetDevice(m->device));
+	uint64_t nt = 0;
+	const int rc = boundary_triangles(m, "lfa_mesher_boundary_size", &nt);
+	if (rc != LFA_OK) return rc;
+	if (n_cells) *n_cells = m->n[0] * m->n[1];
+	if (n_triangles) *n_triangles = nt;
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_download_boundary(lfa_mesher *m, uint8_t *cases, double *face) {
+	if (!m) return LFA_E_INVALID;
+	MSH_HIP(m, hipSetDevice(m->device));
+	uint64_t nt = 0;
+	int rc = boundary_triangles(m, "lfa_mesher_download_boundary", &nt);
+	if (rc == LFA_OK) rc = ensure_face(m);
+	if (rc != LFA_OK) return rc;
+	if (cases)
+		MSH_HIP(m, hipMemcpyAsync(cases, m->occ + (size_t)m->n[0] * m->n[1] * (m->own_lo - m->z0), (size_t)(m->n[0] * m->n[1]),
+		                          hipMemcpyDeviceToHost, m->stream));
+	if (face && nt) MSH_HIP(m, hipMemcpyAsync(face, m->face, (size_t)nt * 24, hipMemcpyDeviceToHost, m->stream));
+	MSH_HIP(m, hipStreamSynchronize(m->stream));
+	return LFA_OK;
+}
+
+/// cases_above / face_above: host memory or memory of m's device (lfa_mesher_window_normals_from).
+static int window_normals(lfa_mesher *m, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above) {
+	if (!m) return LFA_E_INVALID;
+	m->have_normals = false;  // until this call has succeeded
+	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: no current mesh, call lfa_mesher_marching_cubes first");
+	const bool top = m->c_hi == m->n[2];
+	if (top && (cases_above || face_above || n_triangles_above))
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: the window reaches the top of the grid, there is no boundary above it");
+	if (!top && (!cases_above || (!face_above && n_triangles_above)))
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: a window below the top of the grid needs the boundary of the window above");
+	if (n_triangles_above > 5 * m->n[0] * m->n[1])
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: n_triangles_above is more than a layer of cells can hold");
+	MSH_HIP(m, hipSetDevice(m->device));
+	const size_t nv = (size_t)m->n_vertices, nt = (size_t)(m->n_indices / 3), nxy = (size_t)(m->n[0] * m->n[1]);
+	const MeshGrid g = make_grid(m);
+	float ms[2] = {0.0f, 0.0f};
+	for (hipEvent_t &e : m->nrm_ev)
+		if (!e) MSH_HIP(m, hipEventCreate(&e));
+	int rc = LFA_OK;
+	if (nv) rc = grow(m, &m->vnorm, &m->ncap, nv, 24);
+	if (rc != LFA_OK) return rc;
+	MSH_HIP(m, hipEventRecord(m->nrm_ev[0], m->stream));
+	rc = ensure_face(m);
+	if (rc != LFA_OK) return rc;
+	if (!top) {
+		if (!m->b_cases) MSH_HIP(m, hipMalloc(&m->b_cases, nxy));
+		if (!m->b_off) MSH_HIP(m, hipMalloc(&m->b_off, (nxy + 1) * 4));
+		if (!m->b_flag) MSH_HIP(m, hipMalloc(&m->b_flag, 4));
+		rc = grow(m, &m->b_face, &m->bfcap, (size_t)n_triangles_above, 24);
+		if (rc != LFA_OK) return rc;
+		MSH_HIP(m, hipMemcpyAsync(m->b_cases, cases_above, nxy, hipMemcpyDefault, m->stream));
+		if (n_triangles_above)
+			MSH_HIP(m, hipMemcpyAsync(m->b_face, face_above, (size_t)n_triangles_above * 24, hipMemcpyDefault, m->stream));
+		MSH_HIP(m, hipMemsetAsync(m->b_flag, 0xFF, 4, m->stream));
+		hipLaunchKernelGGL(k_boundary_setup, dim3((unsigned)((nxy + 255) / 256)), dim3(256), 0, m->stream, g, (const uint8_t *)m->occ,
+		                   (const uint8_t *)m->b_cases, m->b_off, m->b_flag);
+		MSH_HIP(m, hipGetLastError());
+		rc = scan_u32(m, m->b_off, m->b_off, nxy);
+		if (rc != LFA_OK) return rc;
+		uint32_t total = 0, bad = 0;
+		MSH_HIP(m, hipMemcpyAsync(&total, m->b_off + nxy, 4, hipMemcpyDeviceToHost, m->stream));
+		MSH_HIP(m, hipMemcpyAsync(&bad, m->b_flag, 4, hipMemcpyDeviceToHost, m->stream));
+		MSH_HIP(m, hipEventRecord(m->nrm_ev[1], m->stream));
+		MSH_HIP(m, hipStreamSynchronize(m->stream));
+		MSH_HIP(m, hipEventElapsedTime(&ms[0], m->nrm_ev[0], m->nrm_ev[1]));
+		if ((uint64_t)total != 3 * n_triangles_above) {
+			char msg[200];
+			snprintf(msg, sizeof msg, "lfa_mesher_window_normals: cases_above hold %llu triangles, n_triangles_above is %llu",
+			         (unsigned long long)(total / 3), (unsigned long long)n_triangles_above);
+			return mfail(m, LFA_E_INVALID, msg);
+		}
+		if (bad != 0xFFFFFFFFu) {
+			char msg[240];
+			snprintf(msg, sizeof msg, "lfa_mesher_window_normals: the boundary does not fit this window's mesh (stale, or of another window): "
+			         "first at cell (%llu, %llu) of layer %llu", (unsigned long long)(bad % m->n[0]), (unsigned long long)(bad / m->n[0]),
+			         (unsigned long long)m->c_hi);
+			return mfail(m, LFA_E_INVALID, msg);
+		}
+		MSH_HIP(m, hipEventRecord(m->nrm_ev[0], m->stream));
+	}
+	if (nv && nt) {
+		hipLaunchKernelGGL(k_window_vertex_normals, dim3((unsigned)((m->ncell + 255) / 256)), dim3(256), 0, m->stream, g,
+		                   (const uint8_t *)m->occ, (const uint16_t *)m->created, (const uint32_t *)m->vcount, (const uint32_t *)m->icount,
+		                   (const double *)m->face, m->vsub, (const uint8_t *)m->b_cases, (const uint32_t *)m->b_off,
+		                   (const double *)m->b_face, m->vnorm);
+		MSH_HIP(m, hipGetLastError());
+	}
+	MSH_HIP(m, hipEventRecord(m->nrm_ev[1], m->stream));
+	MSH_HIP(m, hipStreamSynchronize(m->stream));
+	MSH_HIP(m, hipEventElapsedTime(&ms[1], m->nrm_ev[0], m->nrm_ev[1]));
+	m->normals_ms = ms[0] + ms[1];  // (the host's look at the check's result between the two parts is not device time)
+	m->have_normals = true;
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_window_normals(lfa_mesher *m, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above) {
+	return window_normals(m, cases_above, face_above, n_triangles_above);
+}
+
+extern "C" int lfa_mesher_window_normals_from(lfa_mesher *m, lfa_mesher *above) {
+	if (!m || !above) return LFA_E_INVALID;
+	m->have_normals = false;
+	bool fits = above != m && above->own_lo == m->c_hi && above->cs == m->cs;
+	for (int d = 0; d < 3; ++d) fits = fits && above->n[d] == m->n[d] && above->off[d] == m->off[d];
+	if (!fits)
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals_from: `above` is not the window directly above on the same grid "
+		                                "(first own layer, size, offset and cell size must agree)");
+	MSH_HIP(m, hipSetDevice(above->device));
+	uint64_t nt = 0;
+	int rc = boundary_triangles(above, "lfa_mesher_window_normals_from", &nt);
+	if (rc != LFA_OK) return mfail(m, rc, above->err.c_str());
+	const size_t nxy = (size_t)(m->n[0] * m->n[1]);
+	if (above->device != m->device) {  // staged through the host
+		std::vector<uint8_t> cases(nxy);
+		std::vector<double> face(3 * (size_t)nt + 1);
+		rc = lfa_mesher_download_boundary(above, cases.data(), face.data());
+		if (rc != LFA_OK) return mfail(m, rc, above->err.c_str());
+		return window_normals(m, cases.data(), face.data(), nt);
+	}
+	rc = ensure_face(above);
+	if (rc != LFA_OK) return mfail(m, rc, above->err.c_str());
+	MSH_HIP(m, hipStreamSynchronize(above->stream));  // its face vectors are read from m's stream below
+	return window_normals(m, above->occ + nxy * (size_t)(above->own_lo - above->z0), nt ? above->face : nullptr, nt);
 }

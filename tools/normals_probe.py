@@ -13,7 +13,13 @@ and the bytes the device pass must move at the least (24 nv written + 8 ni indic
 of the measured 5.8-6.2 TB/s copy ceiling. The two results are also compared (NaN beside NaN counts as equal).
 Every mesh runs in a child process of its own under a time limit; a failure ends the probe. One JSON line per mesh.
 
-    python tools/normals_probe.py [--meshes dam100,C5] [--reps 20] [--warmup 3] [--out FILE]
+--windows N[,N...]: the same surface cut into N equal z-windows on the one GPU (what the ranks of a slab run hold), normals by
+lfa_mesher_window_normals_from from the top window down. Per window: the device time (lfa_mesher_normals_time; every repetition
+starts from a fresh extraction, so the face vectors are computed inside it) and the bytes of the boundary it exports; the sum
+over the windows stands beside the whole-grid device time and the host loop on the stitched mesh, which is what a slab run
+has to use without it. The stitched normals are compared with the whole grid's. One more JSON line per N.
+
+    python tools/normals_probe.py [--meshes dam100,C5] [--windows 2,8] [--reps 20] [--warmup 3] [--out FILE]
 """
 import argparse
 import json
@@ -74,7 +80,43 @@ def mesh_c5(lfa, np):
 C5_EXPECTED, C5_SLACK = (547320, 1093364), 0.02
 
 
-def child(name, reps, warmup):
+def window_lines(lfa, np, name, m, counts, reps, warmup, whole_ms, host_ms, whole_nrm):
+    """One result per window count: the C5 / dam100 surface from the whole-grid handle's samples, cut into equal z-windows."""
+    values = m.values()
+    nz = m.size[2]
+    out = []
+    for n in counts:
+        bounds = [(nz * k) // n for k in range(n + 1)]
+        ws = []
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            w = lfa.Mesher(m.size, window=(lo, hi), **m.grid)
+            w.set_window_values(values)
+            ws.append(w)
+        per = [[] for _ in ws]
+        for k in range(warmup + reps):
+            for w in ws:
+                w.marching_cubes()  # (a fresh mesh: no cached face vectors)
+            for i in reversed(range(n)):
+                ws[i].compute_window_normals(ws[i + 1] if i + 1 < n else None)
+                if k >= warmup:
+                    per[i].append(ws[i].normals_ms())
+        nrm = lfa.stitch_windows(ws, normals=True)[2]
+        nxy = m.size[0] * m.size[1]
+        blob = [0] + [nxy + 24 * len(w.boundary()[1]) for w in ws[1:]]
+        med = statistics.median
+        totals = [sum(per[i][k] for i in range(n)) for k in range(reps)]
+        out.append({"mesh": name, "windows": n, "bounds": bounds, "reps": reps, "warmup": warmup,
+                    "vertices_per_window": [w._counts[0] for w in ws],
+                    "window_event_ms": [med(x) for x in per], "boundary_bytes_exported": blob,
+                    "windows_total_event_ms": med(totals), "windows_total_event_ms_min_max": [min(totals), max(totals)],
+                    "whole_grid_event_ms": whole_ms, "host_loop_wall_ms": host_ms,
+                    "stitched_equals_whole_grid": bool(np.array_equal(nrm, whole_nrm, equal_nan=True))})
+        for w in ws:
+            w.close()
+    return out
+
+
+def child(name, reps, warmup, windows=()):
     import numpy as np
     import libfluid_amd as lfa
     m, sim = {"dam100": mesh_dam100, "C5": mesh_c5}[name](lfa, np)
@@ -96,7 +138,6 @@ def child(name, reps, warmup):
             ev.append(m.normals_ms())
             compute.append(1e3 * (t1 - t0))
             total.append(1e3 * (t2 - t0))
-    m.close()
     if sim is not None:
         sim.close()
     with tempfile.TemporaryDirectory() as d:
@@ -123,7 +164,12 @@ def child(name, reps, warmup):
            "kernel_shape": "two passes: face vectors (thread per triangle, 24 B per triangle), ordered gather (thread per cell)",
            "device_equals_host_loop": bool(np.array_equal(nrm, host_nrm, equal_nan=True))}
     print(json.dumps(out), flush=True)
-    return 0 if out["device_equals_host_loop"] else 1
+    ok = out["device_equals_host_loop"]
+    for line in window_lines(lfa, np, name, m, windows, reps, warmup, med(ev), med(host), nrm) if ok else []:
+        print(json.dumps(line), flush=True)
+        ok = ok and line["stitched_equals_whole_grid"]
+    m.close()
+    return 0 if ok else 1
 
 
 def main():
@@ -131,16 +177,18 @@ def main():
     ap.add_argument("--meshes", default="dam100,C5")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--windows", default="", help="window counts, e.g. 2,8: also cut every mesh into that many equal z-windows")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.reps < 20 or args.warmup < 3:
         raise SystemExit("at least 20 repetitions after 3 warm-ups")
+    windows = [int(x) for x in args.windows.split(",") if x]
     if args.child:
-        return child(args.child, args.reps, args.warmup)
+        return child(args.child, args.reps, args.warmup, windows)
     for name in args.meshes.split(","):
-        cmd = ["timeout", "-k", "10", str(LIMIT_S[name]), sys.executable, os.path.abspath(__file__), "--child", name,
-               "--reps", str(args.reps), "--warmup", str(args.warmup)]
+        cmd = ["timeout", "-k", "10", str(LIMIT_S[name] + (120 if windows else 0)), sys.executable, os.path.abspath(__file__),
+               "--child", name, "--reps", str(args.reps), "--warmup", str(args.warmup), "--windows", args.windows]
         r = subprocess.run(cmd, capture_output=True, text=True)
         sys.stdout.write(r.stdout)
         sys.stdout.flush()
