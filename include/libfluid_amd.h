@@ -140,7 +140,12 @@ uint64_t lfa_num_fluid_cells(lfa_sim *s);
 int lfa_download_fluid_cells(lfa_sim *s, uint64_t *raw, uint64_t n);
 /* per-cell particle counts (the `count` half of _space_hash, include/fluid/simulation.h:193-197,207), x fastest. */
 int lfa_download_cell_counts(lfa_sim *s, uint32_t *count);
-/* a4-a6: simulation::_transfer_to_grid (src/simulation.cpp:400-412). */
+/* a4-a6: simulation::_transfer_to_grid (src/simulation.cpp:400-412).
+ * RANGE (p2g_variant = LFA_P2G_LDS_BINNED, the default): the scatter accumulates in 64-bit fixed point, and the conversion of one
+ * contribution w (v + C (face - p)), w <= 1, is valid below 2^15. A host stays inside it with
+ *     |v| + |C| * cell_size < 32768      for every particle, in the world units of one step
+ * (PIC / FLIP: |v| alone). Beyond it the face velocities are wrong without any error being reported. LFA_P2G_GLOBAL_ATOMIC
+ * accumulates in fp32 and has no such limit. */
 int lfa_p2g(lfa_sim *s);
 /* a7: gravity loop (src/simulation.cpp:72-78). */
 int lfa_add_gravity(lfa_sim *s, double dt);
@@ -424,8 +429,9 @@ int lfa_get_counts(lfa_sim *s, uint64_t counts[5]);
  * src/pressure_solver.cpp:45-69, is one host loop): [0] kernel launches of one iteration [1] transport calls (neighbour
  * exchanges + all-reduces; 0 on a single domain) of one iteration [2] levels of the multigrid hierarchy (0: another
  * preconditioner) [3] first level that runs inside the single coarse-level launch [4] iterations of the solve
- * [5] transport calls of the whole solve [6] reserved (always 0: the one-launch solve of small systems left the library in
- * round 5) [7] device-side waits given up on this handle so far (0 in a healthy run; after the first one the handle keeps
+ * [5] transport calls of the whole solve [6] not a figure of the solve: how many LDS-binned scatters of lfa_p2g on this handle so far read v and C
+ * through the source index of a deferred binning (the slot of the one-launch solve of small systems, which left the library in
+ * round 5; read-only, for tests of that path) [7] device-side waits given up on this handle so far (0 in a healthy run; after the first one the handle keeps
  * to the launch-per-phase path, and the solve that met it was repeated there). */
 #define LFA_NUM_SOLVER_STATS 8
 int lfa_get_solver_stats(lfa_sim *s, uint64_t stats[LFA_NUM_SOLVER_STATS]);

@@ -219,6 +219,7 @@ struct lfa_sim {
 	uint32_t *vc_src = nullptr;             // index in pb[cur ^ 1] of the particle now at i (valid while vc_pending)
 	size_t vc_extent = 0;                   // records of pb[cur ^ 1] that vc_src may point at (slabs: arrivals append theirs behind)
 	bool vc_pending = false;
+	uint64_t stat_p2g_deferred = 0;         // LDS-binned P2G launches that read v, C through vc_src (lfa_get_solver_stats [6])
 	bool vmax2_valid = false;               // pcg_state[7] holds max |v|^2 of the particles (written by the last G2P, nothing has touched v since)
 	// PIC / FLIP never change C (their P2G does not read it, their G2P does not write it; the hosts' particle records carry it
 	// through): instead of moving 36 bytes per particle with every binning, C is parked in a HOME array indexed by the particle

@@ -449,6 +449,7 @@ int lfa_p2g_run(lfa_sim *s, bool fuse_gravity, double dt) {
 		if (s->n_ptiles) {
 			launch_binned(s, p, pvc, from, s->stage + (size_t)s->p_off * 6 * LFA_HALO_CELLS);
 			LFA_LAUNCH_CHECK(s);
+			if (from) ++s->stat_p2g_deferred;
 		}
 		// particles within one cell of a slab face also contribute to the neighbour rank's faces
 		LFA_TRY(lfa_dist_exchange_p2g_planes(s, s->stage));

@@ -2059,7 +2059,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 extern "C" int lfa_get_solver_stats(lfa_sim *s, uint64_t stats[LFA_NUM_SOLVER_STATS]) {
 	if (!s || !stats) return LFA_E_INVALID;
 	const uint64_t v[LFA_NUM_SOLVER_STATS] = {s->stat_launches_iter, s->stat_transport_iter, s->stat_mg_levels, s->stat_mg_first_co,
-	                                          s->last_iters, s->stat_transport_solve, 0, s->stat_co_aborts};
+	                                          s->last_iters, s->stat_transport_solve, s->stat_p2g_deferred, s->stat_co_aborts};
 	for (int i = 0; i < LFA_NUM_SOLVER_STATS; ++i) stats[i] = v[i];
 	return LFA_OK;
 }
