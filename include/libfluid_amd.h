@@ -124,6 +124,28 @@ int lfa_download_particle_ids(lfa_sim *s, uint32_t *ids, uint64_t n);
 /* Synthetic dam-break block [lo,hi) in cells, 8 jittered particles per cell, generated on the device; bit-identical
  * to libfluid_amd/scenes.py:seed_block. */
 int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_t seed);
+/* simulation::seed_box / seed_sphere (src/simulation.cpp:153-181, seed_func include/fluid/simulation.h:80-115) on the device: the
+ * particles the reference's loop seeds from a pcg32 in state *rng_state, bit for bit and in its order, APPENDED behind the
+ * resident particles (velocity as given, C = 0, ids continuing). Candidate sub-cell i of the loop nest starts at draw 6 i -
+ * three doubles of two 32-bit draws each, as libstdc++'s uniform_real_distribution<double> takes them (generate_canonical:
+ * first draw = low word) - so every candidate is evaluated by its own thread after a jump-ahead of the generator, in the host
+ * loop's fp64 arithmetic, and a compaction in candidate order gives the reference's list (csrc/seed.hip).
+ *   rng_state : raw 64-bit state of the pcg32 (XSH-RR 64/32, multiplier 6364136223846793005, increment 1442695040888963407) on
+ *               entry; on success the state after all 6 x candidates draws, as the host loop leaves it (an empty cell range draws
+ *               nothing). Unchanged on failure.
+ *   flags     : LFA_SEED_DRAW_LTR - the three doubles of a candidate are x, y, z in drawing order (a reference built with a
+ *               compiler that evaluates `vec3d(dist(random), dist(random), dist(random))`, simulation.h:101, left to right);
+ *               default: z, y, x, what g++ does.
+ *   n_seeded  : particles appended (may be NULL)
+ *   positions : NULL, or room for positions_capacity particles: receives the exact fp64 world positions double[3 n_seeded] in
+ *               seeding order (the device keeps an fp32 in-cell fraction: a later download cannot return them).
+ * LFA_E_INVALID, and nothing appended: cell_size unset, density 0 or above 16, positions_capacity below the count, 2^32
+ * particles or more in all, a NULL pointer. LFA_E_UNSUPPORTED on a slab decomposition. */
+enum { LFA_SEED_DRAW_LTR = 1 };
+int lfa_seed_box(lfa_sim *s, const double start[3], const double size[3], const double velocity[3], uint64_t density,
+                 uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions, uint64_t positions_capacity);
+int lfa_seed_sphere(lfa_sim *s, const double centre[3], double radius, const double velocity[3], uint64_t density,
+                    uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions, uint64_t positions_capacity);
 /* Marks cells solid (flat int[3k] triples). lfa_clear_solid_cells resets every cell to non-solid. */
 int lfa_set_solid_cells(lfa_sim *s, const int32_t *xyz, uint64_t k);
 int lfa_clear_solid_cells(lfa_sim *s);

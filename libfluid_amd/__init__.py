@@ -19,6 +19,7 @@ PIC, FLIP_BLEND, APIC = 0, 1, 2
 P2G_LDS_BINNED, P2G_GLOBAL_ATOMIC = 0, 1
 PRECOND_MIC0_TILED, PRECOND_MIC0_EXACT, PRECOND_MULTILEVEL, PRECOND_MULTIGRID = 0, 1, 2, 3
 PCG_F32, PCG_F64 = 0, 1
+SEED_DRAW_LTR = 1
 OK, W_PCG_NOT_CONVERGED = 0, 1
 NUM_TIMERS = 10
 NUM_STEP_TIMERS = 16
@@ -79,6 +80,8 @@ SIGNATURES = {
     "lfa_download_particle_ids": (_int, [_vp, _vp, _u64]),
     "lfa_num_particles": (_u64, [_vp]),
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
+    "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
+    "lfa_seed_sphere": (_int, [_vp, _vp, _dbl, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_set_solid_cells": (_int, [_vp, _vp, _u64]),
     "lfa_clear_solid_cells": (_int, [_vp]),
     "lfa_upload_cells": (_int, [_vp, _vp]),
@@ -578,6 +581,32 @@ class Sim:
         lo = np.asarray(lo, dtype=np.int64)
         hi = np.asarray(hi, dtype=np.int64)
         self._chk(self.lib.lfa_seed_block(self.h, _ptr(lo), _ptr(hi), int(seed)))
+
+    def _seed_shape(self, fn, shape_args, velocity, density, rng_state, flags, positions):
+        vel = np.asarray(velocity, dtype=np.float64)
+        state, n = C.c_uint64(int(rng_state)), C.c_uint64(0)
+        cap, buf = 0, None
+        if positions:  # room for every particle the call can seed; capacity=int bounds it explicitly (lfa_seed_box: LFA_E_INVALID if short)
+            cap = int(positions) if positions is not True else self._seed_bound(density)
+            buf = np.empty((cap, 3), dtype=np.float64)
+        self._chk(fn(self.h, *shape_args, _ptr(vel), int(density), C.byref(state), int(flags), C.byref(n),
+                     None if buf is None else _ptr(buf), cap))
+        return n.value, state.value, None if buf is None else buf[:n.value].copy()
+
+    def _seed_bound(self, density):
+        return self.ncells * int(density) ** 3
+
+    def seed_box(self, start, size, velocity=(0.0, 0.0, 0.0), density=2, rng_state=0, flags=0, positions=False):
+        """simulation::seed_box on the device (lfa_seed_box), appended behind the resident particles. rng_state: raw pcg32 state.
+        positions: True for the exact fp64 seeds (an integer: a buffer of that many particles). Returns
+        (n_seeded, new_state, positions-or-None)."""
+        a, b = np.asarray(start, dtype=np.float64), np.asarray(size, dtype=np.float64)
+        return self._seed_shape(self.lib.lfa_seed_box, (_ptr(a), _ptr(b)), velocity, density, rng_state, flags, positions)
+
+    def seed_sphere(self, centre, radius, velocity=(0.0, 0.0, 0.0), density=2, rng_state=0, flags=0, positions=False):
+        """simulation::seed_sphere on the device (lfa_seed_sphere); see seed_box."""
+        c = np.asarray(centre, dtype=np.float64)
+        return self._seed_shape(self.lib.lfa_seed_sphere, (_ptr(c), float(radius)), velocity, density, rng_state, flags, positions)
 
     def set_solid_cells(self, xyz):
         xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)

@@ -309,6 +309,29 @@ __host__ __device__ inline uint64_t raw_from_blocked(const GridDims &g, uint32_t
 	return (uint64_t)x + (uint64_t)g.nx * ((uint64_t)y + (uint64_t)g.ny * (uint64_t)z);
 }
 
+// ---------------------------------------------------------------------------------------------------- particle ingest
+struct IngestParams {
+	double off[3], h;
+};
+
+/// Position -> (clamped cell, in-cell fraction). The cell is computed in fp64 with a true division exactly like
+/// src/simulation.cpp:253-257 (std::max(pos,0) -> size_t cast -> min(..., size-1)), so keys are bit-exact.
+/// The fraction is fp32 in [0,1]; it is 1.0f only when the position lies on/over the max face (the reference's
+/// unclamped index == size case, src/simulation.cpp:13-23), otherwise it is kept strictly below 1.
+__device__ inline void cell_and_fraction(double pos, double off, double h, int n, int &cell, float &t) {
+	double gp = (pos - off) / h;
+	double m = gp < 0.0 ? 0.0 : gp;
+	int c = m >= (double)n ? n - 1 : (int)m;
+	if (c > n - 1) c = n - 1;
+	double td = gp - (double)c;
+	float tf = (float)td;
+	if (!(tf > 0.0f)) tf = 0.0f;
+	if (td < 1.0 && tf >= 1.0f) tf = 0.99999994f;
+	if (tf > 1.0f) tf = 1.0f;
+	cell = c;
+	t = tf;
+}
+
 // ---------------------------------------------------------------------------------------------------- wave helpers
 /// Binning, pass 1 (core.hip: k_tile_count; particles.hip: the advection of lfa_time_step does it on the way): a wave holds
 /// TC_CHUNKS x 64 consecutive particles, tile[c] = tile of the particle of chunk c in this lane (0xFFFFFFFF: none). One atomic per

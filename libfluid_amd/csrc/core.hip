@@ -519,28 +519,6 @@ int lfa_particles_reserve(lfa_sim *s, size_t n_keep, size_t n_total) {
 	return LFA_OK;
 }
 
-struct IngestParams {
-	double off[3], h;
-};
-
-/// Position -> (clamped cell, in-cell fraction). The cell is computed in fp64 with a true division exactly like
-/// src/simulation.cpp:253-257 (std::max(pos,0) -> size_t cast -> min(..., size-1)), so keys are bit-exact.
-/// The fraction is fp32 in [0,1]; it is 1.0f only when the position lies on/over the max face (the reference's
-/// unclamped index == size case, src/simulation.cpp:13-23), otherwise it is kept strictly below 1.
-__device__ inline void cell_and_fraction(double pos, double off, double h, int n, int &cell, float &t) {
-	double gp = (pos - off) / h;
-	double m = gp < 0.0 ? 0.0 : gp;
-	int c = m >= (double)n ? n - 1 : (int)m;
-	if (c > n - 1) c = n - 1;
-	double td = gp - (double)c;
-	float tf = (float)td;
-	if (!(tf > 0.0f)) tf = 0.0f;
-	if (td < 1.0 && tf >= 1.0f) tf = 0.99999994f;
-	if (tf > 1.0f) tf = 1.0f;
-	cell = c;
-	t = tf;
-}
-
 __global__ void k_ingest(const double *aos, size_t n, ParticleSoA p, GridDims g, IngestParams ip, int slab_lo, int slab_hi) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;

@@ -59,6 +59,20 @@ namespace fluid_amd {
 			std::uint32_t xs = static_cast<std::uint32_t>(((old >> 18u) ^ old) >> 27u), rot = static_cast<std::uint32_t>(old >> 59u);
 			return (xs >> rot) | (xs << ((32u - rot) & 31u));
 		}
+		/// The raw 64-bit state (what lfa_seed_box / lfa_seed_sphere take and hand back).
+		std::uint64_t state() const { return _state; }
+		void set_state(std::uint64_t s) { _state = s; }
+		/// The state after `delta` draws in O(log delta): one draw is an affine map of the state, and the map of 2^j draws is the
+		/// map of 2^(j-1) draws applied twice (the jump-ahead the device seeding gives every candidate, csrc/seed.hip).
+		void advance(std::uint64_t delta) {
+			std::uint64_t cm = 6364136223846793005ull, cp = 1442695040888963407ull, am = 1, ap = 0;
+			for (; delta; delta >>= 1) {
+				if (delta & 1u) { am *= cm; ap = ap * cm + cp; }
+				cp = (cm + 1) * cp;
+				cm *= cm;
+			}
+			_state = am * _state + ap;
+		}
 	private:
 		std::uint64_t _state;
 	};
@@ -174,6 +188,10 @@ namespace fluid_amd {
 		int apic_unscaled_kernel = 1;               ///< 1: the reference's APIC hat on world distances (simulation.cpp:367-369)
 		int pcg_warm_start = 0;                     ///< 1: the PCG starts from the previous step's pressure (0: from p = 0 like the reference)
 		bool overlap_correction = true;             ///< the position correction runs on a second stream beside the pressure solve
+		/// seed_box / seed_sphere run on the device (lfa_seed_box / lfa_seed_sphere): the same particles, no 152-B records built or
+		/// uploaded. The device emulates libstdc++'s uniform_real_distribution: leave it off in a host built against another standard
+		/// library. seed_func / seed_cell always run here: their predicate / count is host code.
+		bool seed_on_device = false;
 		int p2g_variant = LFA_P2G_LDS_BINNED, precond = LFA_PRECOND_MULTIGRID, pcg_dtype = LFA_PCG_F32;
 		double pcg_tau = 0.97, pcg_sigma = 0.25, pcg_tolerance = 1e-6;   ///< pressure_solver.h:39-41
 		std::size_t pcg_max_iterations = 200;                             ///< pressure_solver.h:42
@@ -286,6 +304,13 @@ namespace fluid_amd {
 		void _device_advanced() { _host_stale = true; _grid_stale = true; }
 		bool _push_params();
 		bool _push_solids();
+		/// (not from a callback inside a staged step: the stages that follow need the binning - the host loop's particles get theirs
+		/// with the upload)
+		/// (a density the device does not take, above 16 per axis, stays with the host loop as well)
+		bool _seed_on_device_ready(std::size_t dens) const {
+			return seed_on_device && _dev && _status >= 0 && !_in_step && dens >= 1 && dens <= 16;
+		}
+		template <typename Call> void _seed_device(const Call &call);
 	};
 	static_assert(sizeof(simulation::particle) == 152, "particle layout must match the reference (152-B AoS)");
 
@@ -402,7 +427,28 @@ namespace fluid_amd {
 							}
 				}
 	}
+	/// seed_box / seed_sphere with seed_on_device: the parameters (an upload needs the cell size), then pending host edits (a
+	/// particles().clear() of the caller reaches the device before the new particles are appended), then the call with the
+	/// generator's state; the particles exist on the device only.
+	template <typename Call> void simulation::_seed_device(const Call &call) {
+		if (!_push_params() || !_flush_host_edits()) return;
+		std::uint64_t state = random.state();
+#ifdef LFA_SEED_DRAW_ORDER_LTR
+		const int flags = LFA_SEED_DRAW_LTR;
+#else
+		const int flags = 0;
+#endif
+		if (!_ok(call(&state, flags))) return;
+		random.set_state(state);
+		_host_stale = true;
+		_dev_stale = false;
+	}
 	inline void simulation::seed_box(vec3d start, vec3d size, vec3d vel, std::size_t dens) {
+		if (_seed_on_device_ready(dens)) {
+			const double a[3] = {start.x, start.y, start.z}, b[3] = {size.x, size.y, size.z}, v[3] = {vel.x, vel.y, vel.z};
+			_seed_device([&](std::uint64_t *state, int flags) { return lfa_seed_box(_dev, a, b, v, dens, state, flags, nullptr, nullptr, 0); });
+			return;
+		}
 		vec3d end = start + size;
 		vec3s s = world_position_to_cell_index_unclamped(start), e = world_position_to_cell_index_unclamped(end);
 		seed_func(s, vec3s(e.x - s.x + 1, e.y - s.y + 1, e.z - s.z + 1), [&](vec3d p) {
@@ -410,6 +456,11 @@ namespace fluid_amd {
 		}, vel, dens);
 	}
 	inline void simulation::seed_sphere(vec3d center, double radius, vec3d vel, std::size_t dens) {
+		if (_seed_on_device_ready(dens)) {
+			const double c[3] = {center.x, center.y, center.z}, v[3] = {vel.x, vel.y, vel.z};
+			_seed_device([&](std::uint64_t *state, int flags) { return lfa_seed_sphere(_dev, c, radius, v, dens, state, flags, nullptr, nullptr, 0); });
+			return;
+		}
 		vec3d r(radius, radius, radius);
 		vec3s s = world_position_to_cell_index_unclamped(center - r), e = world_position_to_cell_index_unclamped(center + r);
 		double r2 = radius * radius;
