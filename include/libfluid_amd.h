@@ -140,12 +140,32 @@ int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_
  *   positions : NULL, or room for positions_capacity particles: receives the exact fp64 world positions double[3 n_seeded] in
  *               seeding order (the device keeps an fp32 in-cell fraction: a later download cannot return them).
  * LFA_E_INVALID, and nothing appended: cell_size unset, density 0 or above 16, positions_capacity below the count, 2^32
- * particles or more in all, a NULL pointer. LFA_E_UNSUPPORTED on a slab decomposition. */
-enum { LFA_SEED_DRAW_LTR = 1 };
+ * particles or more in all, a NULL pointer.
+ *
+ * Slab decomposition: LFA_E_UNSUPPORTED, and nothing changed, unless flags carry LFA_SEED_COLLECTIVE. With it the call is
+ * COLLECTIVE in that every rank of the job must make it, with the same arguments and the same *rng_state; no message is sent.
+ * Every rank evaluates every candidate and appends, in candidate order, the accepted ones whose clamped cell - the one the
+ * particle's key holds - lies in its own tile layers: the ranks' lists are a partition of the single-domain list.
+ *   - the id of a particle is its index in the single-domain list, counted on from the job's numbering before the call
+ *     (lfa_download_particle_ids); ids are unique across ranks;
+ *   - n_seeded, positions and positions_capacity speak of the particles THIS rank keeps (it allocates room for those alone);
+ *   - *rng_state advances by 6 x candidates on every rank, also on one that keeps nothing, and the job's numbering by the
+ *     job-wide count; the 2^32 limit is tested against that count, so every rank decides alike;
+ *   - the resident records may be in any state lfa_time_step or lfa_hash_particles leaves them in: records that a hand-over to
+ *     a neighbour rank has left as holes are closed up by the call itself. Like on a single domain the particles are unbinned
+ *     afterwards: lfa_hash_particles (collective) before a download.
+ * What the arguments decide fails on every rank alike, before anything changes. A failure of one rank alone (a short positions
+ * buffer, no memory) leaves THAT handle as it was while the others have seeded: the job must not go on seeding with handles
+ * that disagree - it ends, or starts over from lfa_upload_particles.
+ * On a single domain LFA_SEED_COLLECTIVE changes nothing, so one host code serves 1 and N ranks. */
+enum { LFA_SEED_DRAW_LTR = 1, LFA_SEED_COLLECTIVE = 2 };
 int lfa_seed_box(lfa_sim *s, const double start[3], const double size[3], const double velocity[3], uint64_t density,
                  uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions, uint64_t positions_capacity);
 int lfa_seed_sphere(lfa_sim *s, const double centre[3], double radius, const double velocity[3], uint64_t density,
                     uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions, uint64_t positions_capacity);
+/* The last successful lfa_seed_box / lfa_seed_sphere of this handle: out[0] candidates drawn, out[1] particles accepted in the
+ * WHOLE job (single domain: n_seeded), out[2] id of the first of them. All zero before the first call. */
+int lfa_seed_last(const lfa_sim *s, uint64_t out[3]);
 /* Marks cells solid (flat int[3k] triples). lfa_clear_solid_cells resets every cell to non-solid. */
 int lfa_set_solid_cells(lfa_sim *s, const int32_t *xyz, uint64_t k);
 int lfa_clear_solid_cells(lfa_sim *s);

@@ -19,7 +19,7 @@ PIC, FLIP_BLEND, APIC = 0, 1, 2
 P2G_LDS_BINNED, P2G_GLOBAL_ATOMIC = 0, 1
 PRECOND_MIC0_TILED, PRECOND_MIC0_EXACT, PRECOND_MULTILEVEL, PRECOND_MULTIGRID = 0, 1, 2, 3
 PCG_F32, PCG_F64 = 0, 1
-SEED_DRAW_LTR = 1
+SEED_DRAW_LTR, SEED_COLLECTIVE = 1, 2
 OK, W_PCG_NOT_CONVERGED = 0, 1
 NUM_TIMERS = 10
 NUM_STEP_TIMERS = 16
@@ -82,6 +82,7 @@ SIGNATURES = {
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_seed_sphere": (_int, [_vp, _vp, _dbl, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
+    "lfa_seed_last": (_int, [_vp, C.POINTER(_u64 * 3)]),
     "lfa_set_solid_cells": (_int, [_vp, _vp, _u64]),
     "lfa_clear_solid_cells": (_int, [_vp]),
     "lfa_upload_cells": (_int, [_vp, _vp]),
@@ -599,7 +600,8 @@ class Sim:
     def seed_box(self, start, size, velocity=(0.0, 0.0, 0.0), density=2, rng_state=0, flags=0, positions=False):
         """simulation::seed_box on the device (lfa_seed_box), appended behind the resident particles. rng_state: raw pcg32 state.
         positions: True for the exact fp64 seeds (an integer: a buffer of that many particles). Returns
-        (n_seeded, new_state, positions-or-None)."""
+        (n_seeded, new_state, positions-or-None). On a slab decomposition flags must carry SEED_COLLECTIVE and every rank makes
+        the same call; n_seeded and positions then are what this rank keeps."""
         a, b = np.asarray(start, dtype=np.float64), np.asarray(size, dtype=np.float64)
         return self._seed_shape(self.lib.lfa_seed_box, (_ptr(a), _ptr(b)), velocity, density, rng_state, flags, positions)
 
@@ -607,6 +609,12 @@ class Sim:
         """simulation::seed_sphere on the device (lfa_seed_sphere); see seed_box."""
         c = np.asarray(centre, dtype=np.float64)
         return self._seed_shape(self.lib.lfa_seed_sphere, (_ptr(c), float(radius)), velocity, density, rng_state, flags, positions)
+
+    def seed_last(self):
+        """(candidates, particles accepted in the whole job, id of the first) of the last seed_box / seed_sphere (lfa_seed_last)."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.lfa_seed_last(self.h, C.byref(out)))
+        return tuple(out)
 
     def set_solid_cells(self, xyz):
         xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)

@@ -256,6 +256,7 @@ struct lfa_sim {
 	bool any_coerce = false;
 	uint64_t source_epoch = 0;        // counter of seeding calls: part of the counter-based generator's key
 	uint64_t next_global_id = 0;      // slabs: the id the next seeded particle of the whole job gets (ids are unique across ranks)
+	uint64_t seed_last[3] = {0, 0, 0};  // lfa_seed_last: candidates, particles accepted in the whole job, id of the first (seed.hip)
 
 	// boundary scratch
 	void *io_buf = nullptr;

@@ -12,6 +12,11 @@
 // candidates per wave; their exclusive scan places every wave's particles; k_seed_write evaluates the candidate again (nothing
 // is staged between the passes but that one word per wave) and writes key, fractions, velocity, C = 0 and the id straight into
 // the resident particle arrays, in candidate order - the order of the reference's particle list.
+//
+// Slabs (LFA_SEED_COLLECTIVE): a candidate's draws depend on its number alone, so every rank evaluates every candidate and keeps
+// the accepted ones whose key lies in its own tile layers - no message. The count pass leaves a second word per wave (accepted AND
+// owned), the write pass places a particle by the owned offset and numbers it by the accepted one: the id is the particle's index
+// in the single-domain list, the same on whichever rank it lands. A single domain owns every layer and runs the same kernels.
 #include "common.h"
 
 #include <cmath>
@@ -69,6 +74,7 @@ struct SeedShape {
 	uint32_t density, d3;
 	int nbits;              // significant bits of 6 * (n_cand - 1)
 	int sphere, ltr;
+	int nz, slab_lo, slab_hi;  // cells in z; the tile layers [slab_lo, slab_hi) this rank keeps (single domain: all of them)
 };
 
 /// Candidate i of the loop nest: its position (the host loop's fp64 arithmetic) and whether the predicate accepts it.
@@ -101,42 +107,79 @@ __device__ inline bool seed_candidate(const SeedShape &q, uint64_t i, double (&p
 	return pos[0] > q.lo[0] && pos[1] > q.lo[1] && pos[2] > q.lo[2] && pos[0] < q.hi[0] && pos[1] < q.hi[1] && pos[2] < q.hi[2];
 }
 
-/// Pass 1: accepted candidates per wave (wave w holds the candidates [64 w, 64 w + 64)).
-__global__ void __launch_bounds__(256) k_seed_count(SeedShape q, uint32_t *wave_count) {
-	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-	double pos[3];
-	const bool in = i < q.n_cand && seed_candidate(q, i, pos);
-	const unsigned long long m = __ballot(in);
-	if ((threadIdx.x & 63) == 0 && (i >> 6) < ((q.n_cand + 63) >> 6)) wave_count[i >> 6] = (uint32_t)__popcll(m);
+/// Whether this rank keeps a particle at z: the tile layer of its clamped cell - of its KEY, not of the candidate's loop cell
+/// (a draw may round up into the next cell) - is one of the rank's own. cz, tz: cell_and_fraction of z, as the key takes them.
+__device__ inline bool seed_owned(const SeedShape &q, double z, int &cz, float &tz) {
+	cell_and_fraction(z, q.off[2], q.h, q.nz, cz, tz);
+	return (cz >> 3) >= q.slab_lo && (cz >> 3) < q.slab_hi;
 }
 
-/// Pass 2: the accepted candidates become the particles [base, base + total) in candidate order.
-__global__ void __launch_bounds__(256) k_seed_write(SeedShape q, const uint32_t *wave_off, ParticleSoA p, size_t base, size_t total,
-                                                    GridDims g, float vx, float vy, float vz, double *positions) {
+/// Pass 1: per wave (wave w holds the candidates [64 w, 64 w + 64)) the accepted candidates and those of them this rank keeps.
+__global__ void __launch_bounds__(256) k_seed_count(SeedShape q, uint32_t *wave_accepted, uint32_t *wave_owned) {
 	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
 	double pos[3];
+	int cz;
+	float tz;
 	const bool in = i < q.n_cand && seed_candidate(q, i, pos);
-	const unsigned long long m = __ballot(in);
-	if (!in) return;
-	const int lane = threadIdx.x & 63;
-	const size_t j = (size_t)wave_off[i >> 6] + (size_t)__popcll(m & ((1ull << lane) - 1ull));
-	if (j >= total) return;  // (cannot happen: both passes evaluate the same candidates; keeps a write inside the arrays regardless)
-	const size_t d = base + j;
+	const bool own = in && seed_owned(q, pos[2], cz, tz);
+	const unsigned long long m = __ballot(in), mo = __ballot(own);
+	if ((threadIdx.x & 63) == 0 && (i >> 6) < ((q.n_cand + 63) >> 6)) {
+		wave_accepted[i >> 6] = (uint32_t)__popcll(m);
+		wave_owned[i >> 6] = (uint32_t)__popcll(mo);
+	}
+}
+
+/// Pass 2: the kept candidates become the particles [base, base + total) in candidate order; the id of a particle is id_base + its
+/// index among ALL accepted candidates (single domain: every accepted candidate is kept and id_base = base, so id = slot).
+__global__ void __launch_bounds__(256) k_seed_write(SeedShape q, const uint32_t *accepted_off, const uint32_t *owned_off, ParticleSoA p,
+                                                    size_t base, size_t total, uint64_t id_base, GridDims g, float vx, float vy, float vz,
+                                                    double *positions) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	double pos[3];
 	int c[3];
 	float t[3];
+	const bool in = i < q.n_cand && seed_candidate(q, i, pos);
+	const bool own = in && seed_owned(q, pos[2], c[2], t[2]);
+	const unsigned long long m = __ballot(in), mo = __ballot(own);
+	if (!own) return;  // (a wave that keeps nothing ends here)
+	const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+	const size_t j = (size_t)owned_off[i >> 6] + (size_t)__popcll(mo & below);
+	if (j >= total) return;  // (cannot happen: both passes evaluate the same candidates; keeps a write inside the arrays regardless)
+	const size_t d = base + j;
 	cell_and_fraction(pos[0], q.off[0], q.h, g.nx, c[0], t[0]);
 	cell_and_fraction(pos[1], q.off[1], q.h, g.ny, c[1], t[1]);
-	cell_and_fraction(pos[2], q.off[2], q.h, g.nz, c[2], t[2]);
 	p.key[d] = blocked_index(g, c[0], c[1], c[2]);
 #pragma unroll
 	for (int k = 0; k < 3; ++k) p.t[k][d] = t[k];
 	p.v[0][d] = vx; p.v[1][d] = vy; p.v[2][d] = vz;
 #pragma unroll
 	for (int k = 0; k < 9; ++k) p.c[k][d] = 0.0f;
-	p.id[d] = (uint32_t)d;
+	p.id[d] = (uint32_t)(id_base + (uint64_t)accepted_off[i >> 6] + (uint64_t)__popcll(m & below));
 	if (positions) {
 		positions[3 * j] = pos[0]; positions[3 * j + 1] = pos[1]; positions[3 * j + 2] = pos[2];
 	}
+}
+
+/// Slabs, records with holes (particles handed to a neighbour since the last binning carry an invalid key): the resident
+/// records move to their place among the resident ones (slot = exclusive scan of the valid flags), whole, in storage order.
+__global__ void __launch_bounds__(256) k_seed_valid_flags(const uint32_t *key, size_t n, uint32_t *valid) {
+	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < n) valid[i] = key[i] != 0xFFFFFFFFu ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256) k_seed_close_holes(size_t n, ParticleSoA src, ParticleSoA dst, const uint32_t *slot, size_t n_dst) {
+	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n || src.key[i] == 0xFFFFFFFFu) return;
+	const size_t d = slot[i];
+	if (d >= n_dst) return;  // (cannot happen: the caller has compared the scan's total with the resident count)
+	dst.key[d] = src.key[i];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		dst.t[k][d] = src.t[k][i];
+		dst.v[k][d] = src.v[k][i];
+	}
+#pragma unroll
+	for (int k = 0; k < 9; ++k) dst.c[k][d] = src.c[k][i];
+	dst.id[d] = src.id[i];
 }
 
 // ---------------------------------------------------------------------------------------------------- entry points
@@ -151,9 +194,11 @@ static uint64_t seed_cell_unclamped(double pos, double off, double h) {
 static int seed_shape(lfa_sim *s, SeedShape &q, const double lo[3], const double hi[3], const double velocity[3], uint64_t density,
                       uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions, uint64_t positions_capacity) {
 	if (n_seeded) *n_seeded = 0;
-	if (s->dist)
-		return lfa_fail(s, LFA_E_UNSUPPORTED, "lfa_seed_box / lfa_seed_sphere: not on a slab decomposition (every rank would have to scan "
-		                                      "all candidates and keep those of its own layers)");
+	if (s->dist && !(flags & LFA_SEED_COLLECTIVE))
+		return lfa_fail(s, LFA_E_UNSUPPORTED, "lfa_seed_box / lfa_seed_sphere on a slab decomposition: pass LFA_SEED_COLLECTIVE, and make the "
+		                                      "same call with the same arguments and generator state on every rank (each rank scans all "
+		                                      "candidates and keeps those of its own tile layers)");
+	// ---- what the arguments alone decide: every rank of a collective call fails here alike, or none does
 	if (!(s->prm.cell_size > 0.0)) return lfa_fail(s, LFA_E_INVALID, "set cell_size before seeding");
 	if (density == 0 || density > 16) return lfa_fail(s, LFA_E_INVALID, "seeding density %llu: 1 to 16 per axis", (unsigned long long)density);
 	for (int k = 0; k < 3; ++k)
@@ -179,7 +224,16 @@ static int seed_shape(lfa_sim *s, SeedShape &q, const double lo[3], const double
 	q.n_cand = ext[0] * ext[1] * ext[2] * q.d3;  // (at most 2^32 cells x 2^12)
 	q.state = *rng_state;
 	q.ltr = (flags & LFA_SEED_DRAW_LTR) ? 1 : 0;
-	if (q.n_cand == 0) return LFA_OK;  // an empty range draws nothing
+	q.nz = s->g.nz;
+	q.slab_lo = s->dist ? s->slab_lo : 0;
+	q.slab_hi = s->dist ? s->slab_hi : s->g.ntz;
+	// the id of the call's first particle: the job-wide numbering on slabs, the record index on a single domain
+	const uint64_t id_base = s->dist ? s->next_global_id : (uint64_t)s->np;
+	if (q.n_cand == 0) {  // an empty range draws nothing
+		s->seed_last[0] = s->seed_last[1] = 0;
+		s->seed_last[2] = id_base;
+		return LFA_OK;
+	}
 	if (q.n_cand >= (uint64_t)1 << 38) return lfa_fail(s, LFA_E_INVALID, "seeding: %llu candidates", (unsigned long long)q.n_cand);
 	q.nbits = 64 - __builtin_clzll(6ull * (q.n_cand - 1) | 1ull);
 	const uint64_t new_state = pcg_advance(q.state, 6ull * q.n_cand);
@@ -187,22 +241,37 @@ static int seed_shape(lfa_sim *s, SeedShape &q, const double lo[3], const double
 	LFA_TRY(lfa_corr_commit(s));
 	const size_t n_waves = (size_t)((q.n_cand + 63) >> 6);
 	const unsigned blocks = (unsigned)((q.n_cand + 255) >> 8);
-	uint32_t *wave = nullptr;  // counts, then their exclusive scan | the total
-	LFA_HIP(s, hipMalloc(&wave, (n_waves + 1) * 4));
+	// [accepted per wave, then their exclusive scan | the total] [the same for accepted-and-owned] [records that survive close_holes]
+	uint32_t *wave = nullptr;
+	LFA_HIP(s, hipMalloc(&wave, (2 * (n_waves + 1) + 1) * 4));
+	uint32_t *const acc = wave, *const own = wave + n_waves + 1, *const n_valid = wave + 2 * (n_waves + 1);
 	auto run = [&]() -> int {
-		hipLaunchKernelGGL(k_seed_count, dim3(blocks), dim3(256), 0, s->stream, q, wave);
+		hipLaunchKernelGGL(k_seed_count, dim3(blocks), dim3(256), 0, s->stream, q, acc, own);
 		LFA_LAUNCH_CHECK(s);
-		LFA_TRY(lfa_exclusive_scan_u32(s, wave, wave, n_waves, wave + n_waves));
-		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 97, wave + n_waves, 4, hipMemcpyDeviceToHost, s->stream));
+		LFA_TRY(lfa_exclusive_scan_u32(s, acc, acc, n_waves, acc + n_waves));
+		LFA_TRY(lfa_exclusive_scan_u32(s, own, own, n_waves, own + n_waves));
+		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 97, acc + n_waves, 4, hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 98, own + n_waves, 4, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		const size_t total = s->h_pinned[97], base = s->np;
+		// total_all: accepted in the whole job (the same on every rank); total: kept here; base: resident particles
+		const size_t total_all = s->h_pinned[97], total = s->h_pinned[98], base = s->np;
+		if (id_base + total_all >= ((uint64_t)1 << 32) || base + total >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
 		if (positions && positions_capacity < total)
 			return lfa_fail(s, LFA_E_INVALID, "seeding: room for %llu positions but %zu particles", (unsigned long long)positions_capacity, total);
-		if (base + total >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
-		if (total == 0) {  // every candidate was drawn, none accepted: the handle stays as it is
+		auto done = [&]() {
+			if (s->dist) s->next_global_id = id_base + total_all;
+			s->seed_last[0] = q.n_cand;
+			s->seed_last[1] = total_all;
+			s->seed_last[2] = id_base;
+			if (n_seeded) *n_seeded = total;
 			*rng_state = new_state;
 			return LFA_OK;
-		}
+		};
+		// every candidate was drawn, none kept: the particles stay as they are (slabs: the numbering moves on with the job's)
+		if (total == 0) return done();
+		if (positions) LFA_TRY(lfa_ensure_io(s, total * 24));
+		// records of the current buffer: slabs between a hand-over and the next binning hold the leavers' holes among them
+		size_t n_rec = s->binned ? s->np_live : s->np;
 		if (base == 0) {  // nothing resident (the usual case): nothing to keep, no deferred binning to complete
 			LFA_TRY(lfa_particles_alloc(s, total));
 			s->vc_pending = false;
@@ -211,15 +280,39 @@ static int seed_shape(lfa_sim *s, SeedShape &q, const double lo[3], const double
 		} else {  // append behind the resident particles, like the seeding of lfa_update_sources
 			LFA_TRY(lfa_particles_materialize(s));
 			LFA_TRY(lfa_c_home_restore(s));  // C of the resident particles back beside them: the new ones carry C = 0 in place
-			LFA_TRY(lfa_particles_reserve(s, base, base + total));
+			LFA_TRY(lfa_particles_reserve(s, n_rec, n_rec > base + total ? n_rec : base + total));
+			// (nothing below fails for want of memory: from here on the handle changes)
+			if (s->dist && s->holes) {  // close the holes: [0, base) are the resident records again, the other buffer is free
+				hipLaunchKernelGGL(k_seed_valid_flags, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream,
+				                   (const uint32_t *)s->pb[s->cur].key, n_rec, s->rank);
+				LFA_LAUNCH_CHECK(s);
+				LFA_TRY(lfa_exclusive_scan_u32(s, s->rank, s->rank, n_rec, n_valid));
+				LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 99, n_valid, 4, hipMemcpyDeviceToHost, s->stream));
+				LFA_HIP(s, hipStreamSynchronize(s->stream));
+				// (unbinned, np counted the holes too - lfa_dist_migrate -: then the scan is what tells the resident count)
+				if (s->binned && (size_t)s->h_pinned[99] != base)
+					return lfa_fail(s, LFA_E_INVALID, "seeding: %u resident records but %zu expected", s->h_pinned[99], base);
+				const size_t n_dst = s->h_pinned[99];
+				hipLaunchKernelGGL(k_seed_close_holes, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream, n_rec, s->pb[s->cur],
+				                   s->pb[s->cur ^ 1], (const uint32_t *)s->rank, n_dst);
+				LFA_LAUNCH_CHECK(s);
+				s->cur ^= 1;
+				s->binned = false;  // the order of the last binning is gone
+				s->np = s->np_live = n_dst;
+				s->holes = false;
+			}
 		}
-		if (positions) LFA_TRY(lfa_ensure_io(s, total * 24));
-		hipLaunchKernelGGL(k_seed_write, dim3(blocks), dim3(256), 0, s->stream, q, (const uint32_t *)wave, s->pb[s->cur], base, total, s->g,
-		                   (float)velocity[0], (float)velocity[1], (float)velocity[2], positions ? (double *)s->io_buf : (double *)nullptr);
+		const size_t at = s->np;  // (== base, but for an unbinned slab handle whose holes were just closed)
+		hipLaunchKernelGGL(k_seed_write, dim3(blocks), dim3(256), 0, s->stream, q, (const uint32_t *)acc, (const uint32_t *)own, s->pb[s->cur], at,
+		                   total, id_base, s->g, (float)velocity[0], (float)velocity[1], (float)velocity[2],
+		                   positions ? (double *)s->io_buf : (double *)nullptr);
 		LFA_LAUNCH_CHECK(s);
-		s->np = base + total;
+		s->np = at + total;
 		s->np_live = s->np;
-		s->next_global_id = s->np;
+		s->next_global_id = s->np;  // (slabs: done() puts the job-wide count there)
+		s->holes = false;
+		s->n_arrivals = 0;
+		s->n_ghost_particles = 0;
 		s->binned = false;
 		s->grid_valid = false;
 		s->system_valid = false;
@@ -229,14 +322,18 @@ static int seed_shape(lfa_sim *s, SeedShape &q, const double lo[3], const double
 			LFA_HIP(s, hipMemcpyAsync(positions, s->io_buf, total * 24, hipMemcpyDeviceToHost, s->stream));
 			LFA_HIP(s, hipStreamSynchronize(s->stream));
 		}
-		if (n_seeded) *n_seeded = total;
-		*rng_state = new_state;
-		return LFA_OK;
+		return done();
 	};
 	const int rc = run();
 	// (the release waits for the device, so the kernels that read the scratch are done with it)
 	if (hipFree(wave) != hipSuccess && rc >= 0) return lfa_fail(s, LFA_E_HIP, "releasing the seeding scratch failed");
 	return rc;
+}
+
+extern "C" int lfa_seed_last(const lfa_sim *s, uint64_t out[3]) {
+	if (!s || !out) return LFA_E_INVALID;
+	for (int k = 0; k < 3; ++k) out[k] = s->seed_last[k];
+	return LFA_OK;
 }
 
 extern "C" int lfa_seed_box(lfa_sim *s, const double start[3], const double size[3], const double velocity[3], uint64_t density,
