@@ -121,6 +121,47 @@ uint64_t lfa_num_particles(const lfa_sim *s);
  * after the last lfa_hash_particles, lfa_download_particles writes them in storage order, and this call returns the
  * global id of each record (upload index / index in the seeded block). Single domain: ids[i] = i. */
 int lfa_download_particle_ids(lfa_sim *s, uint32_t *ids, uint64_t n);
+/* -- frame summary: what the hosts read from the particles after every step, without moving the particles ----------------------
+ * The testbed's update_simulation (testbed/main.cpp:50-88) copies simulation::particles(), sums 0.5 |v|^2 - g . x into its "total
+ * energy" (:54-58) and counts the particles of every cell into an occupation grid (:61-67); its
+ * post_grid_to_particle_transfer_callback (:117-123) takes the largest |v|^2. Through lfa_download_particles each of these moves
+ * 152 bytes per particle to the device and 152 back. lfa_frame_stats computes all of them in one pass over the resident key, t and
+ * v arrays (csrc/frame.hip), from the positions and velocities an LFA_DL_POSITIONS download would report, term by term in the
+ * callers' fp64 arithmetic (squared_length: vx vx, += vy vy, += vz vz; dot: gx x, += gy y, += gz z; term = 0.5 sq - dot).
+ *   occupation : NULL, or nx ny nz counts, x fastest (grid3's order), overwritten. Cell of a particle:
+ *                vec3s(vec3i((position - grid_offset) / cell_size)) - a true fp64 division truncated toward zero, counted iff all
+ *                three indices are inside the grid. That is NOT always the cell the particle is binned in (raw_cell_index): the
+ *                reconstructed position off + c h, divided by h again, often lands one cell lower, and the hosts' loop sees that.
+ *   n, n_in_grid, max_speed2, lo, hi and the grid are exactly what the caller's loop over an LFA_DL_POSITIONS download gives.
+ *   energy, energy_abs are sums in a fixed order of the same terms: reproducible (two calls on the same resident state return the
+ *   same bits; no floating-point atomics) and within 2 n 2^-53 energy_abs of any other summation order.
+ * Works in every state lfa_download_particles works in (unbinned, binned, a correction on its second stream, between lfa_advect and
+ * lfa_collide: the moved positions) and changes nothing a later step reads. No particles: LFA_OK, the neutral values below, a
+ * zeroed grid. LFA_E_INVALID, nothing written: cell_size unset, out NULL.
+ * Slab decomposition: local, no message; covers the records this rank owns (never a ghost copy); needs a binned handle like the
+ * download (LFA_E_INVALID otherwise). The ranks' particle sets are a partition, so a job combines the ranks' results itself:
+ * n, n_in_grid, energy, energy_abs and the occupation grids ADD; max_speed2 and hi take the MAXIMUM; lo takes the MINIMUM - the
+ * integer results, the maximum and the box then equal the single domain's exactly.
+ * (The struct has a tag and no typedef: in C a typedef would collide with the function of the same name. Write
+ * `struct lfa_frame_stats st;`.) */
+struct lfa_frame_stats {
+	uint64_t n;            /* resident particles summed over (this rank's own on slabs)            */
+	uint64_t n_in_grid;    /* particles counted by the occupation rule = sum of the occupation grid */
+	double   energy;       /* sum_i (0.5 |v_i|^2 - g . x_i), fp64, g = the handle's gravity parameter */
+	double   energy_abs;   /* sum_i (0.5 |v_i|^2 + |g . x_i|): the condition of that sum            */
+	double   max_speed2;   /* max_i |v_i|^2 (0 for no particles; a NaN speed is skipped, as std::max(maxv, nan) skips it) */
+	double   lo[3], hi[3]; /* bounding box of the positions (+inf / -inf for no particles)          */
+};
+int lfa_frame_stats(lfa_sim *s, struct lfa_frame_stats *out, uint32_t *occupation);
+/* Device milliseconds of the last lfa_frame_stats of this handle (HIP events around the zeroing of the grid, the pass and the final
+ * sum; not the read-back). LFA_E_INVALID when none has run on the device (no call yet, or one with no particles). */
+int lfa_frame_stats_time(lfa_sim *s, double *ms);
+/* The Maya GridNode's cache loop (plugins/maya/nodes/grid_node.cpp:356-364: position of every particle into an MPointArray after
+ * update): double[3 n], n = lfa_num_particles, in the order of lfa_download_particles (single domain: record i = particle i;
+ * slabs: storage order, holes closed) and equal to `position` of an LFA_DL_POSITIONS download bit for bit. 24 bytes per particle
+ * device to host, nothing host to device. LFA_E_INVALID, nothing written: n is not the resident count, cell_size unset, an
+ * unbinned slab handle. */
+int lfa_download_positions(lfa_sim *s, double *xyz, uint64_t n);
 /* Synthetic dam-break block [lo,hi) in cells, 8 jittered particles per cell, generated on the device; bit-identical
  * to libfluid_amd/scenes.py:seed_block. */
 int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_t seed);

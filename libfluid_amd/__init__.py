@@ -56,6 +56,19 @@ class Params(C.Structure):
     ]
 
 
+class FrameStats(C.Structure):
+    """struct lfa_frame_stats (include/libfluid_amd.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("n_in_grid", C.c_uint64),
+        ("energy", C.c_double),
+        ("energy_abs", C.c_double),
+        ("max_speed2", C.c_double),
+        ("lo", C.c_double * 3),
+        ("hi", C.c_double * 3),
+    ]
+
+
 class LibfluidError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libfluid_amd error {code}: {msg}")
@@ -79,6 +92,9 @@ SIGNATURES = {
     "lfa_download_particles": (_int, [_vp, _vp, _u64, _int]),
     "lfa_download_particle_ids": (_int, [_vp, _vp, _u64]),
     "lfa_num_particles": (_u64, [_vp]),
+    "lfa_frame_stats": (_int, [_vp, C.POINTER(FrameStats), _vp]),
+    "lfa_frame_stats_time": (_int, [_vp, C.POINTER(_dbl)]),
+    "lfa_download_positions": (_int, [_vp, _vp, _u64]),
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_seed_sphere": (_int, [_vp, _vp, _dbl, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
@@ -573,6 +589,27 @@ class Sim:
         ids = np.zeros(n, dtype=np.uint32)
         self._chk(self.lib.lfa_download_particle_ids(self.h, _ptr(ids), n))
         return ids
+
+    def frame_stats(self, occupation=True):
+        """(FrameStats, occupation uint32[nz, ny, nx] or None): energy, energy_abs, max |v|^2, the bounding box and the testbed's
+        occupation grid of the resident particles, computed on the device (lfa_frame_stats)."""
+        out = FrameStats()
+        occ = np.empty(self.ncells, dtype=np.uint32) if occupation else None
+        self._chk(self.lib.lfa_frame_stats(self.h, C.byref(out), None if occ is None else _ptr(occ)))
+        return out, None if occ is None else occ.reshape(self.size[2], self.size[1], self.size[0])
+
+    def frame_stats_ms(self):
+        """Device milliseconds of the last frame_stats() (lfa_frame_stats_time)."""
+        out = C.c_double(0.0)
+        self._chk(self.lib.lfa_frame_stats_time(self.h, C.byref(out)))
+        return out.value
+
+    def positions(self):
+        """float64[n, 3]: `pos` of download_particles(), and nothing else (lfa_download_positions)."""
+        n = self.num_particles
+        out = np.empty((n, 3), dtype=np.float64)
+        self._chk(self.lib.lfa_download_positions(self.h, _ptr(out), n))
+        return out
 
     @property
     def num_particles(self):

@@ -263,6 +263,11 @@ struct lfa_sim {
 	size_t io_cap = 0;
 	uint32_t *raw_scan = nullptr;  // nc+1 : raw-order unknown numbering
 
+	// frame summary (frame.hip): one slot per workgroup and field + the reduced result; the events around the last lfa_frame_stats
+	double *frame_part = nullptr;
+	hipEvent_t frame_ev[2] = {nullptr, nullptr};
+	bool frame_timed = false;
+
 	// timing
 	bool timing = false;
 	hipEvent_t ev[48];  // 0-9, 16-18: lfa_step_hot; 20-21: lfa_bench_kernel; 24-..: lfa_time_step (LFA_ST_* boundaries)
@@ -331,6 +336,18 @@ __device__ inline void cell_and_fraction(double pos, double off, double h, int n
 	if (tf > 1.0f) tf = 1.0f;
 	cell = c;
 	t = tf;
+}
+
+/// Key and in-cell fractions -> world position, off + (cell + t) h in fp64: the position a download reports (core.hip: k_export)
+/// and the one the frame summary and lfa_download_positions work on (frame.hip) - one function, so they agree bit for bit.
+__device__ inline void particle_world_position(const GridDims &g, const IngestParams &ip, uint32_t b, float t0, float t1, float t2,
+                                               double (&x)[3]) {
+	int tile = (int)(b >> 9), l = (int)(b & 511), tx, ty, tz;
+	tile_coords(g, tile, tx, ty, tz);
+	const int c[3] = {tx * 8 + (l & 7), ty * 8 + ((l >> 3) & 7), tz * 8 + (l >> 6)};
+	const float t[3] = {t0, t1, t2};
+#pragma unroll
+	for (int k = 0; k < 3; ++k) x[k] = ip.off[k] + ((double)c[k] + (double)t[k]) * ip.h;
 }
 
 // ---------------------------------------------------------------------------------------------------- wave helpers
@@ -447,6 +464,7 @@ int lfa_particles_materialize(lfa_sim *s);  // completes a deferred binning (no-
 int lfa_c_home_restore(lfa_sim *s);         // C back from its home array into the current buffer (no-op unless c_home_valid)
 int lfa_c_home_ensure(lfa_sim *s, size_t n);  // capacity of the home array (keeps the entries of the resident particles)
 int lfa_ensure_io(lfa_sim *s, size_t bytes);
+int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot);  // place of every record among the resident ones (core.hip; nullptr: dense)
 int lfa_pcg_alloc(lfa_sim *s);
 int lfa_number_unknowns(lfa_sim *s);
 

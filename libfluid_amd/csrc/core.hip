@@ -352,7 +352,7 @@ extern "C" void lfa_destroy(lfa_sim *s) {
 	                s->xbuf[0], s->xbuf[1], s->xbuf[2], s->xbuf[3],
 	                s->tile_pslot, s->scan_tmp, s->u, s->v, s->w, s->uo, s->vo, s->wo, s->ctype, s->solid,
 	                s->cell_count, s->stage, s->acc, s->abits, s->vp, s->vr, s->vz, s->vs, s->vpre, s->vq, s->vs2, s->c_as, s->nbr_table,
-	                s->partials, s->pcg_state, s->pcg_hist, s->level_tiles, s->io_buf, s->raw_scan, s->c_diag, s->c_w[0],
+	                s->partials, s->frame_part, s->pcg_state, s->pcg_hist, s->level_tiles, s->io_buf, s->raw_scan, s->c_diag, s->c_w[0],
 	                s->c_w[1], s->c_w[2], s->c_unk, s->c_pre, s->c_r, s->c_x, s->c_r2, s->c_x2, s->a2inv, s->slot_l1,
 	                s->l1_tiles, s->l1_l2};
 	for (void *p : ptrs)
@@ -361,6 +361,8 @@ extern "C" void lfa_destroy(lfa_sim *s) {
 	s->dist = nullptr;
 	lfa_mg_free(s);
 	lfa_pool_nosync_end();
+	for (hipEvent_t e : s->frame_ev)
+		if (e) (void)hipEventDestroy(e);
 	// streams, events and the pinned page are parked for the next lfa_create on this device (a handle whose creation failed
 	// half way is torn down instead)
 	if (s->stream && s->stream2 && s->stream3 && s->ev_fork && s->ev_join && s->ev_cfork && s->ev_cjoin && s->h_pinned) {
@@ -593,22 +595,17 @@ __global__ void k_export(double *aos, size_t n, ParticleSoA p, GridDims g, Inges
 	// slab decomposition: particles migrate between ranks, so a rank's records come out in storage order (ids separately)
 	double *q = aos + (by_slot ? (slot ? (size_t)slot[i] : i) : (size_t)p.id[i]) * 19;
 	if (flags & LFA_DL_POSITIONS) {
-		int tile = (int)(b >> 9), l = (int)(b & 511), tx, ty, tz;
-		tile_coords(g, tile, tx, ty, tz);
-		int c[3] = {tx * 8 + (l & 7), ty * 8 + ((l >> 3) & 7), tz * 8 + (l >> 6)};
+		double x[3];
+		particle_world_position(g, ip, b, p.t[0][i], p.t[1][i], p.t[2][i], x);
 #pragma unroll
 		for (int k = 0; k < 3; ++k) {
-			double x = ip.off[k] + ((double)c[k] + (double)p.t[k][i]) * ip.h;
-			q[k] = x;
-			q[15 + k] = x;
+			q[k] = x[k];
+			q[15 + k] = x[k];
 		}
 		if (have_old) {
-			const uint32_t ob = old.key[i];
-			int otile = (int)(ob >> 9), ol = (int)(ob & 511), ox, oy, oz;
-			tile_coords(g, otile, ox, oy, oz);
-			int oc[3] = {ox * 8 + (ol & 7), oy * 8 + ((ol >> 3) & 7), oz * 8 + (ol >> 6)};
+			particle_world_position(g, ip, old.key[i], old.t[0][i], old.t[1][i], old.t[2][i], x);
 #pragma unroll
-			for (int k = 0; k < 3; ++k) q[15 + k] = ip.off[k] + ((double)oc[k] + (double)old.t[k][i]) * ip.h;
+			for (int k = 0; k < 3; ++k) q[15 + k] = x[k];
 		}
 	}
 #pragma unroll
@@ -620,7 +617,7 @@ __global__ void k_export(double *aos, size_t n, ParticleSoA p, GridDims g, Inges
 
 /// Slabs with holes (particles handed over since the last binning): *slot = device array mapping record i of [0, np_live) to its
 /// place among the resident ones (the binning's rank array, free between two binnings); nullptr when the records are dense.
-static int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot) {
+int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot) {
 	*slot = nullptr;
 	if (!s->dist || !s->holes || !s->np_live) return LFA_OK;
 	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((s->np_live + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->pb[s->cur].key,

@@ -168,6 +168,18 @@ namespace fluid_amd {
 		std::vector<particle> &particles() { _sync_host(); _particles_handed_out = true; return _particles; }
 		const std::vector<particle> &particles() const { const_cast<simulation*>(this)->_sync_host(); return _particles; }
 
+		// What the hosts compute from particles() after every step, computed on the device instead (include/libfluid_amd.h, frame
+		// summary): neither call downloads the particle records or marks the host copy as current - a later particles() still does.
+		// Edits made through particles() / grid() before the call are uploaded first, like before a step.
+		/// lfa_frame_stats' fields (energy, energy_abs, max_speed2, lo, hi, n, n_in_grid) and the testbed's occupation grid
+		/// (testbed/main.cpp:61-67), sized like grid().grid(); empty without `with_occupation`.
+		struct frame_summary : ::lfa_frame_stats {
+			grid3<std::size_t> occupation;
+		};
+		frame_summary frame_stats(bool with_occupation = true);
+		/// `position` of every particle, in the order of particles() (the GridNode's cache loop, grid_node.cpp:356-364).
+		void positions(std::vector<vec3d> &out);
+
 		// callbacks, in calling order (include/fluid/simulation.h:150-175)
 		std::function<void(double)> pre_time_step_callback, post_advection_callback,
 			post_particle_to_grid_transfer_callback, post_gravity_callback;
@@ -300,6 +312,7 @@ namespace fluid_amd {
 			return true;
 		}
 		bool _flush_host_edits();
+		bool _device_current();
 		bool _push_sources();
 		void _device_advanced() { _host_stale = true; _grid_stale = true; }
 		bool _push_params();
@@ -525,6 +538,30 @@ namespace fluid_amd {
 			if (_in_step && !_ok(lfa_hash_particles(_dev))) return false;  // the stages of the running step need the binning
 		}
 		return true;
+	}
+
+	/// The device must hold what the host has edited, and show the particles where the reference's step order has them (a
+	/// correction running ahead is taken back, as for particles()).
+	inline bool simulation::_device_current() {
+		if (_status < 0) return false;
+		if (!_dev) { _status = LFA_E_NO_DEVICE; _error = "no device handle: resize() failed or was not called (there is no CPU fallback)"; return false; }
+		return _push_params() && _take_back_correction() && _flush_host_edits();
+	}
+	inline simulation::frame_summary simulation::frame_stats(bool with_occupation) {
+		frame_summary r{};
+		for (int k = 0; k < 3; ++k) { r.lo[k] = std::numeric_limits<double>::infinity(); r.hi[k] = -r.lo[k]; }
+		if (with_occupation) r.occupation = grid3<std::size_t>(_grid.grid().get_size(), 0);
+		if (!_device_current()) return r;
+		std::vector<std::uint32_t> counts(with_occupation ? detail::cell_count(r.occupation) : 0);
+		if (!_ok(lfa_frame_stats(_dev, &r, with_occupation ? counts.data() : nullptr))) return r;
+		for (std::size_t i = 0; i < counts.size(); ++i) r.occupation[i] = counts[i];
+		return r;
+	}
+	inline void simulation::positions(std::vector<vec3d> &out) {
+		out.clear();
+		if (!_device_current()) return;
+		out.resize(static_cast<std::size_t>(lfa_num_particles(_dev)));
+		if (!_ok(lfa_download_positions(_dev, out.empty() ? nullptr : &out[0].x, out.size()))) out.clear();
 	}
 
 	inline void simulation::time_step(double dt) {
