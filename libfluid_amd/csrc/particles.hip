@@ -151,8 +151,10 @@ __global__ void __launch_bounds__(256) k_tile_has_solid(const uint8_t *solid, in
 		if (threadIdx.x == 0) tile_solid[t] = (uint8_t)(any ? 1 : 0);
 	}
 }
-/// tile_clear[t] = no solid cell within one tile of tile t: a particle that starts in t and moves less than 8 cells per axis
-/// cannot meet one, so its collision handling reduces to the domain walls (which the clamp of the advection already enforces).
+/// tile_clear[t] = no solid cell within one tile of tile t: a particle that starts in t and moves less than 7 cells per axis
+/// neither meets one nor ends in a cell with a solid face neighbour, so its collision handling reduces to the domain walls
+/// (which the clamp of the advection already enforces). (Less than 8 cells would do for the march alone; the skin push-out
+/// looks one cell further.)
 __global__ void k_tile_clear(GridDims g, const uint8_t *tile_solid, uint8_t *tile_clear) {
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= g.nt) return;
@@ -207,12 +209,16 @@ __device__ inline uint32_t advect_one(size_t i, const ParticleSoA &p, const Grid
 		const double lo = mp.skin, hi = (double)nn[d] - mp.skin;
 		to[d] = x < lo ? lo : (hi < x ? hi : x);
 	}
-	// No solid cell within a tile of the start and a move of less than a tile: the march of _detect_collisions meets nothing,
-	// and of its skin push-out only the domain walls remain - where the clamp above has already left the particle at least
-	// `skin` inside (to[d] in [skin, n - skin] => cp >= skin in cell 0, cp <= 1 - skin in cell n - 1). The general path costs
-	// a dependent byte load per crossed cell and per near face; most tiles of a scene are nowhere near a solid.
-	const bool open_water = (tile_clear[key >> 9] & 1) && fabs(to[0] - from[0]) < 8.0 && fabs(to[1] - from[1]) < 8.0 &&
-	                        fabs(to[2] - from[2]) < 8.0;
+	// No solid cell within a tile of the start and a move of less than 7 cells per axis: the march of _detect_collisions meets
+	// nothing, and of its skin push-out only the domain walls remain - where the clamp above has already left the particle at
+	// least `skin` inside (to[d] in [skin, n - skin] => cp >= skin in cell 0, cp <= 1 - skin in cell n - 1). 7, not 8: the
+	// push-out looks at the face neighbours of the END cell. A move of less than 8 cells ends in the neighbouring tile at the
+	// farthest, but possibly in its far cell layer (7.95 -> 15.93), whose neighbour (cell 16) lies two tiles from the start, where
+	// tile_clear says nothing; below 7 cells the end cell is at most 7 + 7 = 14 (or 8 - 7 = 1) and its neighbours are covered.
+	// The general path costs a dependent byte load per crossed cell and per near face; most tiles of a scene are nowhere near a
+	// solid.
+	const bool open_water = (tile_clear[key >> 9] & 1) && fabs(to[0] - from[0]) < 7.0 && fabs(to[1] - from[1]) < 7.0 &&
+	                        fabs(to[2] - from[2]) < 7.0;
 	if (!open_water && mp.collide) collide(g, solid, from, to, mp.skin);
 	int nc[3];
 	float nt[3];
