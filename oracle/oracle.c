@@ -846,7 +846,9 @@ void orc_detect_collisions(void *hh) {
 
 /* simulation::_correct_positions src/simulation.cpp:562-610. Requires the space hash of the current positions.
  * The coincident-particle jitter (:584-587) is random by design in the reference (std::random_device); here such a
- * pair contributes nothing, and the fixtures contain no coincident particles. */
+ * pair (d^2 < 1e-12) contributes nothing. The golden fixtures contain no coincident particles; tests/correction_cases.py holds
+ * near-coincident ones on purpose (close_pairs: pairs down to 2^-20 cells, on both sides of the threshold) and leaves the pairs
+ * below it out of every comparison with the reference. */
 void orc_correct_positions(void *hh, double dt) {
 	orc_ctx *c = (orc_ctx *)hh;
 	const double re = c->h / sqrt(2.0);
