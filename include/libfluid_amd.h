@@ -281,9 +281,10 @@ int lfa_step_hot(lfa_sim *s, double dt, double *residual, uint64_t *iterations);
  *   lfa_update_sources : simulation::_update_sources (:756-765) + the hash_particles that follows it (:64): every cell of an
  *                        active source is topped up to target_density_cubic_root^3 particles (seed_cell, :136-151: uniformly
  *                        random positions inside the cell, the source's velocity, C = 0), counted by the last
- *                        lfa_hash_particles. The positions come from a counter-based generator - the reference draws from
- *                        its pcg32 member in an unspecified argument order, so parity is the particle count
- *                        per cell and every non-random field. New particles get the next ids (download order).
+ *                        lfa_hash_particles. By default the positions come from a counter-based generator: parity is the
+ *                        particle count per cell and every non-random field. lfa_update_sources_rng / lfa_set_source_rng
+ *                        (below) draw them from the simulation's pcg32 instead, bit for bit the reference's particles.
+ *                        New particles get the next ids (download order).
  * lfa_advect_collide applies the velocity coercion of _advect_particles (:227-238: velocity = the source's, C = 0 for every
  * particle inside a cell of an active coercing source) before it moves the particles; lfa_time_step runs the seeding
  * between its two binnings when a source is active. Slab decompositions: every rank is handed the whole list (like the solid
@@ -292,6 +293,35 @@ int lfa_clear_sources(lfa_sim *s);
 int lfa_add_source(lfa_sim *s, const int32_t *xyz, uint64_t k, const double velocity[3], uint64_t target_density_cubic_root,
                    int active, int coerce_velocity);
 int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded);
+/* lfa_update_sources with the reference's own draws: simulation::_update_sources (src/simulation.cpp:756-765) walks the active
+ * sources in order and their cells in list order and calls seed_cell (:136-151), which creates target - count particles at
+ *     position = (grid_offset + vec3d(cell) * cell_size) + vec3d(dist(random), dist(random), dist(random)),
+ * dist = uniform_real_distribution<double>(0, cell_size): six 32-bit draws of the simulation's pcg32 per particle, as libstdc++
+ * takes them. New particle k of a call, counted over all cells in that order, therefore starts at draw 6 k from the state on
+ * entry - k is the exclusive scan of the entries' needs that lfa_update_sources computes anyway -, so every entry jumps there and
+ * draws its own particles (csrc/seed.hip: k_source_seed_rng). Inactive sources and full cells draw nothing. Velocity = (float)
+ * of the source's, C = 0, ids continue in draw order; the call ends with the re-binning, like lfa_update_sources.
+ *   rng_state : raw pcg32 state (see lfa_seed_box) on entry; on success the state after 6 x n_seeded draws. Unchanged on failure.
+ *   flags     : 0 - z gets the first pair of draws, then y, then x (g++'s right-to-left evaluation of :145) - or LFA_SEED_DRAW_LTR.
+ *   positions : NULL, or room for positions_capacity particles: the exact fp64 world positions double[3 n_seeded] in draw order.
+ * What the device stores is what lfa_upload_particles would store for the reference's record: key and fp32 fraction per axis come
+ * from the POSITION, by the upload's rule, not from the source cell. The two differ only when offset + draw rounds up onto the far
+ * face of the source cell: the reference keeps such a particle in the source cell's hash entry (raw_cell_index = the source cell,
+ * :147) for the rest of that one step - its next update_and_hash_particles moves it -, the device bins it in the neighbouring
+ * cell at once. That is the only deviation, and it is the one every uploaded particle is subject to.
+ * LFA_E_INVALID, records and state untouched: no lfa_hash_particles since the particles last changed, cell_size unset, a NULL
+ * rng_state, positions_capacity below the count, 2^32 particles or more in all. LFA_E_UNSUPPORTED on a slab decomposition (the
+ * ranks' needs would have to be merged into one scan: DESIGN.md).
+ *
+ * lfa_set_source_rng(on = 1) makes this the behaviour of the plain lfa_update_sources and of the seeding inside lfa_time_step:
+ * they draw from the state kept in the handle and advance it (the host class carries `pcg32 random`, include/fluid/simulation.h:177,
+ * through a step this way); lfa_get_source_rng reads the mode and the state back. on = 0, the default, restores the counter-based
+ * generator exactly as before, its sequence included. LFA_E_UNSUPPORTED: on = 1 on a handle with a transport; when a transport is
+ * attached after the mode was switched on, lfa_update_sources and lfa_time_step refuse instead, before they change anything. */
+int lfa_update_sources_rng(lfa_sim *s, uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions,
+                           uint64_t positions_capacity);
+int lfa_set_source_rng(lfa_sim *s, int on, uint64_t rng_state, int flags);
+int lfa_get_source_rng(const lfa_sim *s, int *on, uint64_t *rng_state);
 int lfa_advect_collide(lfa_sim *s, double dt);
 int lfa_correct_collide(lfa_sim *s, double dt);
 /* The same two stages with the collision handling split off, for hosts that install post_advection_callback or

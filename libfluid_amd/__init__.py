@@ -169,6 +169,9 @@ SIGNATURES = {
     "lfa_clear_sources": (_int, [_vp]),
     "lfa_add_source": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _int]),
     "lfa_update_sources": (_int, [_vp, C.POINTER(_u64)]),
+    "lfa_update_sources_rng": (_int, [_vp, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
+    "lfa_set_source_rng": (_int, [_vp, _int, _u64, _int]),
+    "lfa_get_source_rng": (_int, [_vp, C.POINTER(_int), C.POINTER(_u64)]),
     "lfa_advect_collide": (_int, [_vp, _dbl]),
     "lfa_advect": (_int, [_vp, _dbl]),
     "lfa_correct": (_int, [_vp, _dbl]),
@@ -770,6 +773,7 @@ class Sim:
     # -- particle stages around the hot path, full step ---------------------------------------------------
     def clear_sources(self):
         self._chk(self.lib.lfa_clear_sources(self.h))
+        self._source_targets = []
 
     def add_source(self, cells, velocity=(0.0, 0.0, 0.0), density_cubic_root=2, active=True, coerce_velocity=False):
         """fluid::source (data_structures/source.h:12-22): cells as int32[k,3]."""
@@ -777,12 +781,36 @@ class Sim:
         vel = np.asarray(velocity, dtype=np.float64)
         self._chk(self.lib.lfa_add_source(self.h, _ptr(xyz), xyz.shape[0], _ptr(vel), int(density_cubic_root), int(active),
                                           int(coerce_velocity)))
+        self._source_targets = getattr(self, "_source_targets", []) + [xyz.shape[0] * int(density_cubic_root) ** 3]
 
     def update_sources(self):
         """_update_sources + hash_particles (src/simulation.cpp:63-64); returns the number of particles created."""
         n = C.c_uint64(0)
         self._chk(self.lib.lfa_update_sources(self.h, C.byref(n)))
         return n.value
+
+    def update_sources_rng(self, rng_state, flags=0, positions=False):
+        """update_sources with the reference's draws from the pcg32 in `rng_state` (lfa_update_sources_rng). positions: True for
+        the exact fp64 positions in draw order (an integer: a buffer of that many particles). Returns
+        (n_seeded, new_state, positions-or-None)."""
+        state, n = C.c_uint64(int(rng_state)), C.c_uint64(0)
+        cap, buf = 0, None
+        if positions:  # (True: no call creates more than the targets of the listed cells together)
+            cap = int(positions) if positions is not True else sum(getattr(self, "_source_targets", []))
+            buf = np.empty((cap, 3), dtype=np.float64)
+        self._chk(self.lib.lfa_update_sources_rng(self.h, C.byref(state), int(flags), C.byref(n),
+                                                  None if buf is None else _ptr(buf), cap))
+        return n.value, state.value, None if buf is None else buf[:n.value].copy()
+
+    def set_source_rng(self, on, rng_state=0, flags=0):
+        """update_sources() and the seeding inside time_step() draw from (and advance) this pcg32 state (lfa_set_source_rng)."""
+        self._chk(self.lib.lfa_set_source_rng(self.h, int(bool(on)), int(rng_state), int(flags)))
+
+    def get_source_rng(self):
+        """(on, state) of set_source_rng (lfa_get_source_rng)."""
+        on, state = C.c_int(0), C.c_uint64(0)
+        self._chk(self.lib.lfa_get_source_rng(self.h, C.byref(on), C.byref(state)))
+        return bool(on.value), state.value
 
     def advect(self, dt):
         self._chk(self.lib.lfa_advect(self.h, float(dt)))

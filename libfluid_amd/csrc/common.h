@@ -255,6 +255,11 @@ struct lfa_sim {
 	uint8_t *coerce_map = nullptr;    // [ncp] 1 + index of the LAST active coercing source that lists the cell, 0: none
 	bool any_coerce = false;
 	uint64_t source_epoch = 0;        // counter of seeding calls: part of the counter-based generator's key
+	// lfa_set_source_rng: lfa_update_sources (and the one inside lfa_time_step) draws the positions from this pcg32 state, as the
+	// reference's seed_cell does, instead of the counter-based generator (off: the default)
+	bool src_rng_on = false;
+	uint64_t src_rng_state = 0;
+	int src_rng_flags = 0;            // 0 or LFA_SEED_DRAW_LTR
 	uint64_t next_global_id = 0;      // slabs: the id the next seeded particle of the whole job gets (ids are unique across ranks)
 	uint64_t seed_last[3] = {0, 0, 0};  // lfa_seed_last: candidates, particles accepted in the whole job, id of the first (seed.hip)
 
@@ -545,3 +550,9 @@ inline int lfa_corr_commit(lfa_sim *s) {
 /// for ever.
 void lfa_co_gate_handle(int device, int delta);
 int lfa_sources_sync(lfa_sim *s);  // flattens `sources` to the device arrays if they changed (particles.hip)
+/// The seeding kernel of lfa_update_sources with the reference's pcg32 draws (seed.hip, beside the generator): the `total` new
+/// particles of the flattened entries (src_cell / src_of / src_need, `off` = the exclusive scan of src_need) are written to the
+/// records [base, base + total) of the current buffer; positions_dev: nullptr or room for 3 x total doubles on the device.
+/// *state_after = `state` advanced by 6 x total draws.
+int lfa_source_seed_rng(lfa_sim *s, const uint32_t *off, size_t base, size_t total, uint64_t id_base, uint64_t state, int ltr,
+                        double *positions_dev, uint64_t *state_after);

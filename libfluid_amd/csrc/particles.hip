@@ -1107,9 +1107,17 @@ int lfa_sources_sync(lfa_sim *s) {
 	return LFA_OK;
 }
 
-extern "C" int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded) {
-	if (!s) return LFA_E_INVALID;
+/// lfa_update_sources. rng_state == nullptr: positions from the counter-based generator (k_source_seed); else the reference's
+/// draws from the pcg32 in *rng_state (seed.hip: k_source_seed_rng; single domain only), advanced on success.
+static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, int flags, double *positions, uint64_t positions_capacity) {
 	if (n_seeded) *n_seeded = 0;
+	if (rng_state) {
+		if (s->dist)
+			return lfa_fail(s, LFA_E_UNSUPPORTED, "fluid sources that draw from the pcg32 on a slab decomposition: the ranks' needs "
+			                                      "would have to be merged into one scan (not implemented)");
+		if (!(s->prm.cell_size > 0.0)) return lfa_fail(s, LFA_E_INVALID, "set cell_size before seeding");
+		if (flags & ~LFA_SEED_DRAW_LTR) return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: flags 0 or LFA_SEED_DRAW_LTR");
+	}
 	if (!s->binned) return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources: call lfa_hash_particles first");
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
@@ -1152,6 +1160,10 @@ extern "C" int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded) {
 	}
 	if (!total_all) return LFA_OK;  // every source cell is full: the binning stands
 	if (s->np_live + total >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
+	if (rng_state && positions && positions_capacity < total)
+		return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: room for %llu positions but %zu particles",
+		                (unsigned long long)positions_capacity, total);
+	if (rng_state && positions) LFA_TRY(lfa_ensure_io(s, total * 24));
 	const size_t base = s->np_live;
 	LFA_TRY(lfa_particles_materialize(s));  // the new particles bring their own v / C: a deferred binning is completed first
 	LFA_TRY(lfa_particles_reserve(s, base, base + total));  // keeps the live records
@@ -1160,8 +1172,15 @@ extern "C" int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded) {
 		for (int k = 0; k < 9 && total; ++k)
 			LFA_HIP(s, hipMemsetAsync(s->c_home + (size_t)k * s->c_home_cap + id_base, 0, total * 4, s->stream));
 	}
-	++s->source_epoch;
-	if (total) {
+	uint64_t state_after = 0;
+	if (rng_state) {
+		LFA_TRY(lfa_source_seed_rng(s, off, base, total, id_base, *rng_state, (flags & LFA_SEED_DRAW_LTR) ? 1 : 0,
+		                            positions ? (double *)s->io_buf : (double *)nullptr, &state_after));
+		if (positions) LFA_HIP(s, hipMemcpyAsync(positions, s->io_buf, total * 24, hipMemcpyDeviceToHost, s->stream));
+	} else {
+		++s->source_epoch;
+	}
+	if (total && !rng_state) {
 		hipLaunchKernelGGL(k_source_seed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
 		                   (const uint32_t *)s->src_of, (const uint32_t *)s->src_need, (const uint32_t *)off, n, (const float *)s->src_vel,
 		                   s->pb[s->cur], base, 0x5EED50ull + s->source_epoch * 0x632BE59BD9B4E019ull, id_base);
@@ -1171,7 +1190,44 @@ extern "C" int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded) {
 	s->np = s->np_live;
 	s->vmax2_valid = false;  // the new particles carry their source's velocity
 	if (n_seeded) *n_seeded = total;
-	return lfa_hash_particles(s);  // the reference re-hashes after seeding (src/simulation.cpp:64)
+	const int rc = lfa_hash_particles(s);  // the reference re-hashes after seeding (src/simulation.cpp:64)
+	if (rc >= 0 && rng_state) {
+		if (positions) LFA_HIP(s, hipStreamSynchronize(s->stream));
+		*rng_state = state_after;
+	}
+	return rc;
+}
+
+extern "C" int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded) {
+	if (!s) return LFA_E_INVALID;
+	if (s->src_rng_on) return update_sources(s, n_seeded, &s->src_rng_state, s->src_rng_flags, nullptr, 0);
+	return update_sources(s, n_seeded, nullptr, 0, nullptr, 0);
+}
+
+extern "C" int lfa_update_sources_rng(lfa_sim *s, uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions,
+                                      uint64_t positions_capacity) {
+	if (!s) return LFA_E_INVALID;
+	if (!rng_state) return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: rng_state is NULL");
+	return update_sources(s, n_seeded, rng_state, flags, positions, positions_capacity);
+}
+
+extern "C" int lfa_set_source_rng(lfa_sim *s, int on, uint64_t rng_state, int flags) {
+	if (!s) return LFA_E_INVALID;
+	if (on && s->dist)
+		return lfa_fail(s, LFA_E_UNSUPPORTED, "fluid sources that draw from the pcg32 on a slab decomposition: the ranks' needs would "
+		                                      "have to be merged into one scan (not implemented)");
+	if (on && (flags & ~LFA_SEED_DRAW_LTR)) return lfa_fail(s, LFA_E_INVALID, "lfa_set_source_rng: flags 0 or LFA_SEED_DRAW_LTR");
+	s->src_rng_on = on != 0;
+	s->src_rng_state = on ? rng_state : 0;
+	s->src_rng_flags = on ? flags : 0;
+	return LFA_OK;
+}
+
+extern "C" int lfa_get_source_rng(const lfa_sim *s, int *on, uint64_t *rng_state) {
+	if (!s) return LFA_E_INVALID;
+	if (on) *on = s->src_rng_on ? 1 : 0;
+	if (rng_state) *rng_state = s->src_rng_state;
+	return LFA_OK;
 }
 
 /// Which tiles are nowhere near a solid cell / a domain wall (k_tile_clear): recomputed when the solid mask has changed.
@@ -1495,6 +1551,8 @@ extern "C" int lfa_correct_collide_undo(lfa_sim *s) {
 int lfa_g2p_stale(lfa_sim *s);  // grid_ops.hip
 extern "C" int lfa_time_step(lfa_sim *s, double dt, double *residual, uint64_t *iterations) {
 	if (!s) return LFA_E_INVALID;
+	if (s->src_rng_on && s->dist)  // (before anything moves: lfa_update_sources would refuse in the middle of the step)
+		return lfa_fail(s, LFA_E_UNSUPPORTED, "lfa_time_step: fluid sources that draw from the pcg32 (lfa_set_source_rng) on a slab decomposition");
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
 	const bool tm = s->timing;

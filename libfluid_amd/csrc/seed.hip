@@ -182,6 +182,77 @@ __global__ void __launch_bounds__(256) k_seed_close_holes(size_t n, ParticleSoA 
 	dst.id[d] = src.id[i];
 }
 
+// ---------------------------------------------------------------------------------------------------- fluid sources
+/// simulation::seed_cell (src/simulation.cpp:136-151) for the flattened entries of lfa_update_sources, with the reference's draws:
+/// new particle k of the call, counted over all entries in order, starts at draw 6 k, and off[i] - the exclusive scan of the
+/// entries' needs - is the number of the entry's first particle. One thread per entry: one jump to 6 off[i], then the entry's
+/// need[i] particles drawn one after the other, as the host loop draws them. position = (grid_offset + cell * cell_size) + draws
+/// in fp64; key and fractions are what an upload of that position stores (cell_and_fraction), not the source cell: a sum that
+/// rounds up to the cell's far face lands in the next cell.
+__global__ void __launch_bounds__(256) k_source_seed_rng(const uint32_t *cell, const uint32_t *src_of, const uint32_t *need,
+                                                         const uint32_t *off, size_t n, const float *src_vel, ParticleSoA p, size_t base,
+                                                         size_t total, uint64_t id_base, GridDims g, IngestParams ip, uint64_t state,
+                                                         int nbits, int ltr, double *positions) {
+	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t cnt = need[i], first = off[i], b = cell[i];
+	if (!cnt) return;
+	uint64_t st = state;
+	const uint64_t dist = 6ull * first;
+	for (int j = 0; j < nbits; ++j)
+		if ((dist >> j) & 1ull) st = st * c_jump.mult[j] + c_jump.plus[j];
+	int tx, ty, tz;
+	tile_coords(g, (int)(b >> 9), tx, ty, tz);
+	const int l = (int)(b & 511), cc[3] = {tx * 8 + (l & 7), ty * 8 + ((l >> 3) & 7), tz * 8 + (l >> 6)}, nn[3] = {g.nx, g.ny, g.nz};
+	double corner[3];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) corner[k] = ip.off[k] + (double)cc[k] * ip.h;
+	const float *vel = src_vel + 3 * src_of[i];
+	const float v0 = vel[0], v1 = vel[1], v2 = vel[2];
+	for (uint32_t j = 0; j < cnt; ++j) {
+		const size_t r = (size_t)first + j;
+		if (r >= total) return;  // (cannot happen: total is the scan's sum; keeps a write inside the arrays regardless)
+		// `vec3d(dist(random), dist(random), dist(random))` (:145): g++ evaluates right to left, so z gets the first draw
+		double u[3];
+		if (ltr) {
+			u[0] = seed_uniform(st, ip.h); u[1] = seed_uniform(st, ip.h); u[2] = seed_uniform(st, ip.h);
+		} else {
+			u[2] = seed_uniform(st, ip.h); u[1] = seed_uniform(st, ip.h); u[0] = seed_uniform(st, ip.h);
+		}
+		const size_t d = base + r;
+		int c[3];
+		float t[3];
+#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			const double x = corner[k] + u[k];
+			cell_and_fraction(x, ip.off[k], ip.h, nn[k], c[k], t[k]);
+			p.t[k][d] = t[k];
+			if (positions) positions[3 * r + k] = x;
+		}
+		p.key[d] = blocked_index(g, c[0], c[1], c[2]);
+		p.v[0][d] = v0; p.v[1][d] = v1; p.v[2][d] = v2;
+#pragma unroll
+		for (int k = 0; k < 9; ++k) p.c[k][d] = 0.0f;
+		p.id[d] = (uint32_t)(id_base + (uint64_t)r);
+	}
+}
+
+int lfa_source_seed_rng(lfa_sim *s, const uint32_t *off, size_t base, size_t total, uint64_t id_base, uint64_t state, int ltr,
+                        double *positions_dev, uint64_t *state_after) {
+	const size_t n = s->n_src_entries;
+	*state_after = pcg_advance(state, 6ull * total);
+	if (!n || !total) return LFA_OK;
+	IngestParams ip;
+	for (int k = 0; k < 3; ++k) ip.off[k] = s->prm.grid_offset[k];
+	ip.h = s->prm.cell_size;
+	const int nbits = 64 - __builtin_clzll(6ull * total | 1ull);
+	hipLaunchKernelGGL(k_source_seed_rng, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
+	                   (const uint32_t *)s->src_of, (const uint32_t *)s->src_need, off, n, (const float *)s->src_vel, s->pb[s->cur], base,
+	                   total, id_base, s->g, ip, state, nbits, ltr, positions_dev);
+	LFA_LAUNCH_CHECK(s);
+	return LFA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------- entry points
 /// simulation::world_position_to_cell_index_unclamped (src/simulation.cpp:190-197): max(g, 0) before the conversion.
 /// (Anything at or beyond 2^62 cells - far outside every grid - stops there: the conversion itself would not be defined.)

@@ -204,6 +204,11 @@ namespace fluid_amd {
 		/// uploaded. The device emulates libstdc++'s uniform_real_distribution: leave it off in a host built against another standard
 		/// library. seed_func / seed_cell always run here: their predicate / count is host code.
 		bool seed_on_device = false;
+		/// The fluid sources of a step draw their positions from `random`, as the reference's seed_cell does (lfa_set_source_rng):
+		/// time_step hands random.state() to the device before the seeding and reads it back after it, so `sources` create the
+		/// reference's particles and leave `random` where the reference leaves it. Off: the device's counter-based generator, and
+		/// `random` untouched by sources. The same libstdc++ caveat as seed_on_device; single domain only.
+		bool sources_draw_from_random = false;
 		int p2g_variant = LFA_P2G_LDS_BINNED, precond = LFA_PRECOND_MULTIGRID, pcg_dtype = LFA_PCG_F32;
 		double pcg_tau = 0.97, pcg_sigma = 0.25, pcg_tolerance = 1e-6;   ///< pressure_solver.h:39-41
 		std::size_t pcg_max_iterations = 200;                             ///< pressure_solver.h:42
@@ -324,6 +329,9 @@ namespace fluid_amd {
 			return seed_on_device && _dev && _status >= 0 && !_in_step && dens >= 1 && dens <= 16;
 		}
 		template <typename Call> void _seed_device(const Call &call);
+		bool _source_rng_pushed = false;  ///< the handle's source mode was switched on by this class (sources_draw_from_random)
+		bool _push_source_rng();
+		void _pull_source_rng();
 	};
 	static_assert(sizeof(simulation::particle) == 152, "particle layout must match the reference (152-B AoS)");
 
@@ -501,6 +509,24 @@ namespace fluid_amd {
 		return true;
 	}
 
+	/// sources_draw_from_random: the generator's state goes to the handle before a step and comes back after its seeding.
+	inline bool simulation::_push_source_rng() {
+		if (!sources_draw_from_random && !_source_rng_pushed) return true;  // never asked for: the handle is left alone
+#ifdef LFA_SEED_DRAW_ORDER_LTR
+		const int flags = LFA_SEED_DRAW_LTR;
+#else
+		const int flags = 0;
+#endif
+		if (!_ok(lfa_set_source_rng(_dev, sources_draw_from_random ? 1 : 0, random.state(), flags))) return false;
+		_source_rng_pushed = sources_draw_from_random;
+		return true;
+	}
+	inline void simulation::_pull_source_rng() {
+		if (!_source_rng_pushed) return;
+		std::uint64_t state = random.state();
+		if (_ok(lfa_get_source_rng(_dev, nullptr, &state))) random.set_state(state);
+	}
+
 	/// Brings the device up to date with whatever the host did through particles() / grid() / the seeding functions since the last
 	/// device stage. Between steps only the solid mask of the grid matters (the P2G rebuilds velocities and air / fluid types);
 	/// inside a staged step an edited grid is uploaded whole and edited particles are re-uploaded and re-binned.
@@ -575,7 +601,9 @@ namespace fluid_amd {
 		std::uint64_t iters = 0;
 		if (!_any_stage_callback()) {
 			// ---- the whole step in one call (src/simulation.cpp:43-125 incl. sources)
+			if (!_push_source_rng()) return;
 			if (_ok(lfa_time_step(_dev, dt, &residual, &iters))) _device_advanced();
+			_pull_source_rng();
 			return;
 		}
 		// ---- the same device stages one by one, callbacks in the reference's order between them. After every callback the
@@ -592,8 +620,12 @@ namespace fluid_amd {
 		bool ok = (post_advection_callback
 		               ? stage(lfa_advect(_dev, dt)) && after(post_advection_callback) && stage(lfa_collide(_dev))
 		               : stage(lfa_advect_collide(_dev, dt))) &&
-		          stage(lfa_hash_particles(_dev)) && (sources.empty() || stage(lfa_update_sources(_dev, nullptr))) &&
-		          stage(lfa_p2g(_dev)) && after(post_particle_to_grid_transfer_callback);
+		          stage(lfa_hash_particles(_dev));
+		if (ok && !sources.empty()) {  // (`random` is handed over right at the seeding: callbacks before and after it may draw from it too)
+			ok = _push_source_rng() && stage(lfa_update_sources(_dev, nullptr));
+			_pull_source_rng();
+		}
+		ok = ok && stage(lfa_p2g(_dev)) && after(post_particle_to_grid_transfer_callback);
 		// From here to the correction the reference's stages touch the grid only (simulation.cpp:82-99): the correction starts now,
 		// on the second stream (see _corr_in_flight).
 		// (not with a post_correction_callback: the correction then runs where the reference has it, split from its collisions)

@@ -1,0 +1,67 @@
+"""simulation::_update_sources / seed_cell restated in numpy, built on tests/seed_model.py: what the g++-built reference's fluid
+sources seed from its pcg32 (src/simulation.cpp:756-765, 136-151).
+
+The active sources are walked in order and their cells in list order. A cell whose hash count is below target = root^3 gets
+target - count particles at (grid_offset + cell * cell_size) + (dx, dy, dz), each coordinate a uniform_real_distribution<double>(0,
+cell_size) of two 32-bit draws, z drawn first (g++ evaluates the arguments of `vec3d(dist(random), dist(random), dist(random))`
+right to left); then the count is set to target UNCONDITIONALLY (:150), also when it was larger. So new particle k of a call
+starts at draw 6 k. tests/test_source_model.py pins this model to the compiled reference and to its recorded particles; the GPU
+tests take their expected values from it."""
+import numpy as np
+
+from tests import seed_model as sm
+
+
+def update_sources(grid_size, cell_size, offset, counts, sources, state, ltr=False):
+    """counts: the space hash's particle count per cell (x fastest, any shape with nx * ny * nz entries; not modified).
+    sources: [(cells int[k, 3], velocity, target_density_cubic_root, active), ...] (further entries are ignored).
+    Returns (positions float64[n, 3] in draw order, source_cells int64[n, 3], velocities float64[n, 3], state afterwards)."""
+    nx, ny, nz = (int(v) for v in grid_size)
+    count = np.array(counts, dtype=np.int64).reshape(-1).copy()
+    assert count.size == nx * ny * nz
+    off, h = np.asarray(offset, dtype=np.float64), np.float64(cell_size)
+    pos, cells, vels = [], [], []
+    for src in sources:
+        xyz, velocity, root, active = src[0], src[1], int(src[2]), bool(src[3])
+        if not active:
+            continue
+        target = root ** 3
+        for cell in np.asarray(xyz, dtype=np.int64).reshape(-1, 3):
+            raw = int(cell[0] + nx * (cell[1] + ny * cell[2]))
+            k = target - int(count[raw])
+            count[raw] = target
+            if k <= 0:
+                continue
+            st = sm._advance_each(state, np.arange(k, dtype=np.uint64) * np.uint64(6))
+            u0, st = sm._uniform(st, h)
+            u1, st = sm._uniform(st, h)
+            u2, st = sm._uniform(st, h)
+            u = (u0, u1, u2) if ltr else (u2, u1, u0)  # g++: the last argument is evaluated first
+            corner = off + cell.astype(np.float64) * h  # one multiply, then one add, per axis
+            pos.append(np.stack([corner[a] + u[a] for a in range(3)], axis=1))
+            cells.append(np.broadcast_to(cell, (k, 3)))
+            vels.append(np.broadcast_to(np.asarray(velocity, dtype=np.float64), (k, 3)))
+            state = sm.advance(state, 6 * k)
+    if not pos:
+        return np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64), np.zeros((0, 3)), state
+    return np.concatenate(pos), np.concatenate(cells), np.concatenate(vels), state
+
+
+def cell_counts(grid_size, cell_size, offset, positions):
+    """The count half of the space hash after update_and_hash_particles (src/simulation.cpp:251-291): clamped cell of every
+    position, true division in fp64."""
+    n = np.asarray(grid_size, dtype=np.int64)
+    g = (np.asarray(positions, dtype=np.float64).reshape(-1, 3) - np.asarray(offset, dtype=np.float64)) / np.float64(cell_size)
+    idx = np.minimum(np.maximum(g, 0.0).astype(np.int64), n - 1)
+    raw = idx[:, 0] + n[0] * (idx[:, 1] + n[1] * idx[:, 2])
+    return np.bincount(raw, minlength=int(n.prod()))
+
+
+def records(positions, velocities):
+    """The 152-byte records seed_cell builds (raw_cell_index is recomputed by the device on upload)."""
+    from libfluid_amd.scenes import PARTICLE_DTYPE
+    out = np.zeros(len(positions), dtype=PARTICLE_DTYPE)
+    out["pos"] = positions
+    out["old_pos"] = positions
+    out["vel"] = velocities
+    return out
