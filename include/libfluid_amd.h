@@ -310,18 +310,47 @@ int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded);
  * :147) for the rest of that one step - its next update_and_hash_particles moves it -, the device bins it in the neighbouring
  * cell at once. That is the only deviation, and it is the one every uploaded particle is subject to.
  * LFA_E_INVALID, records and state untouched: no lfa_hash_particles since the particles last changed, cell_size unset, a NULL
- * rng_state, positions_capacity below the count, 2^32 particles or more in all. LFA_E_UNSUPPORTED on a slab decomposition (the
- * ranks' needs would have to be merged into one scan: DESIGN.md).
+ * rng_state, positions_capacity below the count, 2^32 particles or more in all, a flag other than the two named here.
+ * LFA_E_UNSUPPORTED, and nothing changed, on a slab decomposition without LFA_SEED_COLLECTIVE.
+ *
+ * Slab decomposition, flags | LFA_SEED_COLLECTIVE: the call is a COLLECTIVE. Every rank makes it with the same *rng_state and
+ * flags after the same lfa_add_source list (every rank is handed the whole list anyway). The draw number of an entry is its offset
+ * among the new particles of ALL ranks in source order, and that order interleaves the ranks' entries: the ranks' needs are summed
+ * into one vector over the job-wide entry list and scanned on every rank. That is ONE transport call per seeding call (an
+ * all-reduce of one float per entry; none when no active source lists a cell), beside those of the re-binning that ends the call.
+ * The ranks' new particles are a partition of the single-domain call's:
+ *   - a particle belongs to the rank whose tile layers hold its KEY - the clamped cell of its fp64 position, not the source cell
+ *     (the ownership rule of the collective lfa_seed_box): a position that rounds onto the far z face of a slab's top cell layer
+ *     is created on the rank above;
+ *   - the id of a particle is the job's numbering before the call plus its index in the single-domain draw order; ids are unique
+ *     across ranks, and each rank's records and positions follow that order;
+ *   - n_seeded, positions and positions_capacity speak of the particles THIS rank keeps;
+ *   - *rng_state advances by 6 x the job-wide count on every rank, also on one that keeps nothing, and the job's numbering by
+ *     the job-wide count; the 2^32 limit is tested against that count, so every rank decides alike;
+ *   - the call ends with the re-binning on every rank, or - nothing to create anywhere - on none.
+ * What the arguments and the job-wide count decide fails on every rank alike, before anything changes. A failure of one rank
+ * alone (a short positions buffer, no memory) leaves THAT handle as it was; its peers have seeded, and their re-binning - which
+ * needs every rank - fails with LFA_E_HIP (the in-process transport reports the lost peer at once, the others when their wait
+ * runs out). As for lfa_seed_box the job must not go on with handles that disagree: it ends, or starts over from
+ * lfa_upload_particles. On a single domain LFA_SEED_COLLECTIVE changes nothing, so one host code serves 1 and N ranks.
  *
  * lfa_set_source_rng(on = 1) makes this the behaviour of the plain lfa_update_sources and of the seeding inside lfa_time_step:
  * they draw from the state kept in the handle and advance it (the host class carries `pcg32 random`, include/fluid/simulation.h:177,
  * through a step this way); lfa_get_source_rng reads the mode and the state back. on = 0, the default, restores the counter-based
- * generator exactly as before, its sequence included. LFA_E_UNSUPPORTED: on = 1 on a handle with a transport; when a transport is
- * attached after the mode was switched on, lfa_update_sources and lfa_time_step refuse instead, before they change anything. */
+ * generator exactly as before, its sequence included (on slabs: ids in rank order). flags as above; with LFA_SEED_COLLECTIVE the
+ * mode is accepted on a handle with a transport - every rank switches it on with the same state - and stays valid when a transport
+ * is attached later. LFA_E_UNSUPPORTED: on = 1 without LFA_SEED_COLLECTIVE on a handle with a transport; when a transport is
+ * attached after the mode was switched on without it, lfa_update_sources and lfa_time_step refuse instead, before they change
+ * anything.
+ *
+ * lfa_source_last: the last successful source seeding of this handle that drew from the pcg32 (a call that created nothing drew
+ * nothing and leaves it alone): out[0] particles created in the WHOLE job, out[1] particles kept by this handle (single domain:
+ * the same), out[2] id of the first of them. All zero before the first such call. */
 int lfa_update_sources_rng(lfa_sim *s, uint64_t *rng_state, int flags, uint64_t *n_seeded, double *positions,
                            uint64_t positions_capacity);
 int lfa_set_source_rng(lfa_sim *s, int on, uint64_t rng_state, int flags);
 int lfa_get_source_rng(const lfa_sim *s, int *on, uint64_t *rng_state);
+int lfa_source_last(const lfa_sim *s, uint64_t out[3]);
 int lfa_advect_collide(lfa_sim *s, double dt);
 int lfa_correct_collide(lfa_sim *s, double dt);
 /* The same two stages with the collision handling split off, for hosts that install post_advection_callback or

@@ -172,6 +172,7 @@ SIGNATURES = {
     "lfa_update_sources_rng": (_int, [_vp, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_set_source_rng": (_int, [_vp, _int, _u64, _int]),
     "lfa_get_source_rng": (_int, [_vp, C.POINTER(_int), C.POINTER(_u64)]),
+    "lfa_source_last": (_int, [_vp, C.POINTER(_u64 * 3)]),
     "lfa_advect_collide": (_int, [_vp, _dbl]),
     "lfa_advect": (_int, [_vp, _dbl]),
     "lfa_correct": (_int, [_vp, _dbl]),
@@ -792,7 +793,8 @@ class Sim:
     def update_sources_rng(self, rng_state, flags=0, positions=False):
         """update_sources with the reference's draws from the pcg32 in `rng_state` (lfa_update_sources_rng). positions: True for
         the exact fp64 positions in draw order (an integer: a buffer of that many particles). Returns
-        (n_seeded, new_state, positions-or-None)."""
+        (n_seeded, new_state, positions-or-None). On a slab decomposition flags must carry SEED_COLLECTIVE and every rank makes
+        the same call (one thread per rank: the call exchanges a message); n_seeded and positions then are what this rank keeps."""
         state, n = C.c_uint64(int(rng_state)), C.c_uint64(0)
         cap, buf = 0, None
         if positions:  # (True: no call creates more than the targets of the listed cells together)
@@ -803,8 +805,16 @@ class Sim:
         return n.value, state.value, None if buf is None else buf[:n.value].copy()
 
     def set_source_rng(self, on, rng_state=0, flags=0):
-        """update_sources() and the seeding inside time_step() draw from (and advance) this pcg32 state (lfa_set_source_rng)."""
+        """update_sources() and the seeding inside time_step() draw from (and advance) this pcg32 state (lfa_set_source_rng).
+        Slab decompositions: flags carry SEED_COLLECTIVE, and every rank sets the same state."""
         self._chk(self.lib.lfa_set_source_rng(self.h, int(bool(on)), int(rng_state), int(flags)))
+
+    def source_last(self):
+        """(particles created in the whole job, particles kept by this handle, id of the first) of the last source seeding that
+        drew from the pcg32 (lfa_source_last)."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.lfa_source_last(self.h, C.byref(out)))
+        return tuple(out)
 
     def get_source_rng(self):
         """(on, state) of set_source_rng (lfa_get_source_rng)."""

@@ -259,7 +259,25 @@ struct lfa_sim {
 	// reference's seed_cell does, instead of the counter-based generator (off: the default)
 	bool src_rng_on = false;
 	uint64_t src_rng_state = 0;
-	int src_rng_flags = 0;            // 0 or LFA_SEED_DRAW_LTR
+	int src_rng_flags = 0;            // LFA_SEED_DRAW_LTR and / or LFA_SEED_COLLECTIVE
+	// slabs, collective pcg32 seeding (LFA_SEED_COLLECTIVE): the job-wide flattened entry list - the same dedup and `lo` rule over
+	// ALL cells, so the own entries above are a subsequence of it - and this rank's CANDIDATE entries, the ones that can leave a
+	// particle in its tile layers: source cell z in [8 slab_lo - 1, 8 slab_hi] (a position that rounds onto a cell's far face
+	// takes the next cell's key; one that rounds below its corner - offsets that are no binary fractions - the previous cell's).
+	// One allocation, in 32-bit words (SourceSlab::words); `mode` 0: every particle of the entry stays here whatever it draws
+	// (the cells below and above are the rank's own, or the grid ends there), 1: the count pass has to draw them.
+	struct SourceSlab {
+		uint32_t *own_gidx = nullptr;  // [n_src_entries] global index of the own entry
+		uint32_t *cell = nullptr, *of = nullptr, *gidx = nullptr, *mode = nullptr;  // [n_cand] candidates, in global order
+		float *need_f = nullptr;       // [n_global] the all-reduced vector: one non-zero contributor per slot
+		uint32_t *need = nullptr;      // [n_global] the same as integers
+		uint32_t *first = nullptr;     // [n_global + 1] exclusive scan: number of the entry's first draw triple | job-wide total
+		uint32_t *keep = nullptr;      // [n_cand] particles of the candidate this rank keeps
+		uint32_t *keep_off = nullptr;  // [n_cand + 1] their exclusive scan | the rank's total
+		uint32_t *words = nullptr;
+		size_t n_cand = 0, n_global = 0;
+	} src_slab;
+	uint64_t source_last[3] = {0, 0, 0};  // lfa_source_last: created in the whole job, kept here, id of the first
 	uint64_t next_global_id = 0;      // slabs: the id the next seeded particle of the whole job gets (ids are unique across ranks)
 	uint64_t seed_last[3] = {0, 0, 0};  // lfa_seed_last: candidates, particles accepted in the whole job, id of the first (seed.hip)
 
@@ -508,6 +526,9 @@ struct lfa_dist {
 		return allreduce_buf_impl(s, dev, count, dtype, is_max);
 	}
 	uint64_t calls = 0;
+	/// A collective call fails on this rank alone, after a message has already been exchanged: the peers' next transport call
+	/// must not wait for this rank (in-process transport: it fails at once; the others have no such channel - their peers time out).
+	virtual void give_up() { broken = true; }
 	bool broken = false;  // a transport call failed, or the job abandons this transport (lfa_dist_abandon): close without waiting for peers
 	virtual int exchange_impl(lfa_sim *s, const void *send_lo, size_t n_send_lo, void *recv_lo, size_t n_recv_lo,
 	                          const void *send_hi, size_t n_send_hi, void *recv_hi, size_t n_recv_hi) = 0;
@@ -556,3 +577,11 @@ int lfa_sources_sync(lfa_sim *s);  // flattens `sources` to the device arrays if
 /// *state_after = `state` advanced by 6 x total draws.
 int lfa_source_seed_rng(lfa_sim *s, const uint32_t *off, size_t base, size_t total, uint64_t id_base, uint64_t state, int ltr,
                         double *positions_dev, uint64_t *state_after);
+/// The same on a slab decomposition (LFA_SEED_COLLECTIVE), for the candidate entries of lfa_sim::src_slab once `need` and `first`
+/// hold the job-wide needs and their scan. _count: keep / keep_off (and *kept = the rank's total, read back) - the particles
+/// whose KEY lies in the own tile layers. _write: those particles, at the records [base, base + kept) in draw order, numbered
+/// id_base + their draw number; positions_dev compacted alike.
+int lfa_source_slab_count(lfa_sim *s, size_t total_all, uint64_t state, int ltr, size_t *kept);
+int lfa_source_slab_write(lfa_sim *s, size_t base, size_t kept, size_t total_all, uint64_t id_base, uint64_t state, int ltr,
+                          double *positions_dev);
+uint64_t lfa_pcg32_advance(uint64_t state, uint64_t draws);  // seed.hip: the pcg32 state after `draws` 32-bit draws

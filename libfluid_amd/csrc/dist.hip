@@ -585,6 +585,10 @@ struct lfa_hub {
 namespace {
 struct LocalDist : lfa_dist {
 	lfa_hub *hub = nullptr;
+	void give_up() override {
+		broken = true;
+		hub->fail();
+	}
 	int exchange_impl(lfa_sim *s, const void *send_lo, size_t n_send_lo, void *recv_lo, size_t n_recv_lo, const void *send_hi,
 	             size_t n_send_hi, void *recv_hi, size_t n_recv_hi) override {
 		LFA_HIP(s, hipStreamSynchronize(s->stream));

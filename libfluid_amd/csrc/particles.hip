@@ -952,6 +952,16 @@ __global__ void k_source_need(const uint32_t *cell, const uint32_t *lo, const ui
 	const uint32_t have = lo[i] != 0xFFFFFFFFu ? lo[i] : (tile_flag[b >> 9] ? cell_count[b] : 0u);
 	need[i] = target[i] > have ? target[i] - have : 0u;
 }
+/// Slabs, pcg32 draws: the own entries' needs into their slots of the (zeroed) vector over the job-wide entry list, as floats
+/// for the all-reduce - a need is at most 4096, so they are exact - and the reduced vector back to integers.
+__global__ void k_source_need_scatter(const uint32_t *need, const uint32_t *gidx, size_t n, float *all) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) all[gidx[i]] = (float)need[i];
+}
+__global__ void k_source_need_gather(const float *all, size_t n, uint32_t *need) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) need[i] = (uint32_t)all[i];
+}
 __device__ inline uint64_t mix64(uint64_t x) {
 	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
 	x ^= x >> 27; x *= 0x94D049BB133111EBull;
@@ -1026,6 +1036,9 @@ int lfa_sources_sync(lfa_sim *s) {
 	// map covers the whole grid (a particle's cell is always an owned one)
 	const int own_zlo = s->dist ? s->slab_lo * 8 : 0, own_zhi = s->dist ? s->slab_hi * 8 : s->g.nz;
 	std::vector<uint32_t> cell, lo, target, of, ccell, csrc;
+	// slabs: global index of the own entries; cell, source, global index and mode of the candidates (lfa_sim::SourceSlab)
+	std::vector<uint32_t> own_g, k_cell, k_of, k_g, k_mode;
+	uint32_t n_global = 0;
 	std::vector<float> vel;
 	{
 		std::vector<std::pair<uint32_t, uint32_t>> seen;  // (cell, target of its latest entry), kept sorted by cell
@@ -1038,18 +1051,29 @@ int lfa_sources_sync(lfa_sim *s) {
 			for (size_t i = 0; i + 2 < h.xyz.size(); i += 3) {
 				const uint32_t b = blocked_index(s->g, h.xyz[i], h.xyz[i + 1], h.xyz[i + 2]);
 				if (h.coerce) coerce.push_back(std::make_pair(b, (uint32_t)si + 1));
-				if (h.xyz[i + 2] < own_zlo || h.xyz[i + 2] >= own_zhi) continue;  // another rank's cell
+				// (the rule runs over every rank's cells: a cell has one owner, so the own entries are the ones a walk over the own
+				// cells alone gives, and every rank numbers the entries of the whole job alike)
+				const int z = h.xyz[i + 2];
+				const bool own = z >= own_zlo && z < own_zhi;
 				auto it = std::lower_bound(seen.begin(), seen.end(), std::make_pair(b, 0u),
 				                           [](const std::pair<uint32_t, uint32_t> &a, const std::pair<uint32_t, uint32_t> &c) { return a.first < c.first; });
+				uint32_t from = 0xFFFFFFFFu;
 				if (it != seen.end() && it->first == b) {
-					const uint32_t prev = it->second;
+					from = it->second;
 					it->second = tgt;
-					if (tgt > prev) {
-						cell.push_back(b); lo.push_back(prev); target.push_back(tgt); of.push_back((uint32_t)si);
-					}
+					if (tgt <= from) continue;
 				} else {
 					seen.insert(it, std::make_pair(b, tgt));
-					cell.push_back(b); lo.push_back(0xFFFFFFFFu); target.push_back(tgt); of.push_back((uint32_t)si);
+				}
+				const uint32_t gi = n_global++;
+				if (own) {
+					cell.push_back(b); lo.push_back(from); target.push_back(tgt); of.push_back((uint32_t)si);
+					own_g.push_back(gi);
+				}
+				if (s->dist && z >= own_zlo - 1 && z <= own_zhi) {
+					const int below = z > 0 ? z - 1 : 0, above = z + 1 < s->g.nz ? z + 1 : s->g.nz - 1;
+					k_cell.push_back(b); k_of.push_back((uint32_t)si); k_g.push_back(gi);
+					k_mode.push_back(own && below >= own_zlo && above < own_zhi ? 0u : 1u);
 				}
 			}
 		}
@@ -1102,26 +1126,120 @@ int lfa_sources_sync(lfa_sim *s) {
 		LFA_HIP(s, hipMemcpy(s->src_of, of.data(), n * 4, hipMemcpyHostToDevice));
 	}
 	s->n_src_entries = n;
+	if (s->src_slab.words) LFA_HIP(s, hipFree(s->src_slab.words));
+	s->src_slab = lfa_sim::SourceSlab();
+	if (s->dist && n_global) {
+		lfa_sim::SourceSlab &q = s->src_slab;
+		const size_t nk = k_cell.size(), ng = n_global;
+		LFA_HIP(s, hipMalloc(&q.words, (n + 6 * nk + 3 * ng + 2) * 4));
+		uint32_t *w = q.words;
+		auto take = [&](size_t m) { uint32_t *at = w; w += m; return at; };
+		q.own_gidx = take(n); q.cell = take(nk); q.of = take(nk); q.gidx = take(nk); q.mode = take(nk);
+		q.need_f = (float *)take(ng); q.need = take(ng); q.first = take(ng + 1); q.keep = take(nk); q.keep_off = take(nk + 1);
+		if (n) LFA_HIP(s, hipMemcpy(q.own_gidx, own_g.data(), n * 4, hipMemcpyHostToDevice));
+		if (nk) {
+			LFA_HIP(s, hipMemcpy(q.cell, k_cell.data(), nk * 4, hipMemcpyHostToDevice));
+			LFA_HIP(s, hipMemcpy(q.of, k_of.data(), nk * 4, hipMemcpyHostToDevice));
+			LFA_HIP(s, hipMemcpy(q.gidx, k_g.data(), nk * 4, hipMemcpyHostToDevice));
+			LFA_HIP(s, hipMemcpy(q.mode, k_mode.data(), nk * 4, hipMemcpyHostToDevice));
+		}
+		q.n_cand = nk;
+		q.n_global = ng;
+	}
 	s->sources_built = s->sources;
 	s->sources_valid = true;
 	return LFA_OK;
 }
 
+/// lfa_update_sources_rng with LFA_SEED_COLLECTIVE on a slab decomposition (the checks of update_sources are done, the entry lists
+/// are current). ONE transport call - the all-reduce of the needs over the job-wide entry list -, none when no source lists an
+/// active entry; the re-binning that ends the call has its own.
+static int update_sources_collective(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, int flags, double *positions,
+                                     uint64_t positions_capacity) {
+	const lfa_sim::SourceSlab &q = s->src_slab;
+	const size_t n = s->n_src_entries, ng = q.n_global;
+	const uint64_t id_base = s->next_global_id, state = *rng_state;
+	const int ltr = (flags & LFA_SEED_DRAW_LTR) ? 1 : 0;
+	if (!ng) return LFA_OK;  // no entry anywhere: nothing to create, no draw, no message
+	LFA_HIP(s, hipMemsetAsync(q.need_f, 0, ng * 4, s->stream));
+	if (n) {
+		hipLaunchKernelGGL(k_source_need, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
+		                   (const uint32_t *)s->src_lo, (const uint32_t *)s->src_target, n, (const uint32_t *)s->cell_count,
+		                   (const uint32_t *)s->tile_flag, s->src_need);
+		hipLaunchKernelGGL(k_source_need_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream,
+		                   (const uint32_t *)s->src_need, (const uint32_t *)q.own_gidx, n, q.need_f);
+		LFA_LAUNCH_CHECK(s);
+	}
+	LFA_TRY(s->dist->allreduce_buf(s, q.need_f, ng, LFA_RED_F32, false));
+	hipLaunchKernelGGL(k_source_need_gather, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s->stream, (const float *)q.need_f, ng,
+	                   q.need);
+	LFA_LAUNCH_CHECK(s);
+	LFA_TRY(lfa_exclusive_scan_u32(s, q.need, q.first, ng, q.first + ng));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 104, q.first + ng, 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	const size_t total_all = s->h_pinned[104];
+	// ---- what the job-wide count decides: every rank decides alike
+	if (!total_all) return LFA_OK;  // every source cell of the job is full: no draw, the binning stands
+	if (id_base + total_all >= ((uint64_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
+	// ---- from here a failure is this rank's alone: its peers must not wait for it in the re-binning
+	size_t kept = 0;
+	const size_t base = s->np_live;
+	auto seed = [&]() -> int {
+		LFA_TRY(lfa_source_slab_count(s, total_all, state, ltr, &kept));
+		if (base + kept >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
+		if (positions && positions_capacity < kept)
+			return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: room for %llu positions but this rank keeps %zu particles",
+			                (unsigned long long)positions_capacity, kept);
+		if (positions) LFA_TRY(lfa_ensure_io(s, kept * 24));
+		LFA_TRY(lfa_particles_materialize(s));
+		LFA_TRY(lfa_particles_reserve(s, base, base + kept));
+		if (s->c_home_valid) {  // C = 0 for every new id of the job: the ids a rank keeps are no contiguous range
+			LFA_TRY(lfa_c_home_ensure(s, (size_t)(id_base + total_all)));
+			for (int k = 0; k < 9; ++k)
+				LFA_HIP(s, hipMemsetAsync(s->c_home + (size_t)k * s->c_home_cap + id_base, 0, total_all * 4, s->stream));
+		}
+		LFA_TRY(lfa_source_slab_write(s, base, kept, total_all, id_base, state, ltr, positions ? (double *)s->io_buf : (double *)nullptr));
+		if (positions && kept) LFA_HIP(s, hipMemcpyAsync(positions, s->io_buf, kept * 24, hipMemcpyDeviceToHost, s->stream));
+		return LFA_OK;
+	};
+	const int rc_seed = seed();
+	if (rc_seed < 0) {
+		s->dist->give_up();
+		return rc_seed;
+	}
+	s->next_global_id = id_base + total_all;
+	s->np_live = base + kept;
+	s->np = s->np_live;
+	s->vmax2_valid = false;
+	if (n_seeded) *n_seeded = kept;
+	const int rc = lfa_hash_particles(s);
+	if (rc >= 0) {
+		if (positions) LFA_HIP(s, hipStreamSynchronize(s->stream));
+		*rng_state = lfa_pcg32_advance(state, 6ull * total_all);
+		s->source_last[0] = total_all;
+		s->source_last[1] = kept;
+		s->source_last[2] = id_base;
+	}
+	return rc;
+}
+
 /// lfa_update_sources. rng_state == nullptr: positions from the counter-based generator (k_source_seed); else the reference's
-/// draws from the pcg32 in *rng_state (seed.hip: k_source_seed_rng; single domain only), advanced on success.
+/// draws from the pcg32 in *rng_state (seed.hip: k_source_seed_rng; slabs: update_sources_collective), advanced on success.
 static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, int flags, double *positions, uint64_t positions_capacity) {
 	if (n_seeded) *n_seeded = 0;
 	if (rng_state) {
-		if (s->dist)
-			return lfa_fail(s, LFA_E_UNSUPPORTED, "fluid sources that draw from the pcg32 on a slab decomposition: the ranks' needs "
-			                                      "would have to be merged into one scan (not implemented)");
+		if (flags & ~(LFA_SEED_DRAW_LTR | LFA_SEED_COLLECTIVE))
+			return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: flags LFA_SEED_DRAW_LTR, LFA_SEED_COLLECTIVE or none");
+		if (s->dist && !(flags & LFA_SEED_COLLECTIVE))
+			return lfa_fail(s, LFA_E_UNSUPPORTED, "fluid sources that draw from the pcg32 on a slab decomposition: pass LFA_SEED_COLLECTIVE, "
+			                                      "and make the same call with the same generator state on every rank");
 		if (!(s->prm.cell_size > 0.0)) return lfa_fail(s, LFA_E_INVALID, "set cell_size before seeding");
-		if (flags & ~LFA_SEED_DRAW_LTR) return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: flags 0 or LFA_SEED_DRAW_LTR");
 	}
 	if (!s->binned) return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources: call lfa_hash_particles first");
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
 	LFA_TRY(lfa_sources_sync(s));
+	if (rng_state && s->dist) return update_sources_collective(s, n_seeded, rng_state, flags, positions, positions_capacity);
 	const size_t n = s->n_src_entries;
 	if (!n && !s->dist) return LFA_OK;
 	size_t total = 0;
@@ -1194,6 +1312,8 @@ static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, i
 	if (rc >= 0 && rng_state) {
 		if (positions) LFA_HIP(s, hipStreamSynchronize(s->stream));
 		*rng_state = state_after;
+		s->source_last[0] = s->source_last[1] = total;
+		s->source_last[2] = id_base;
 	}
 	return rc;
 }
@@ -1213,13 +1333,20 @@ extern "C" int lfa_update_sources_rng(lfa_sim *s, uint64_t *rng_state, int flags
 
 extern "C" int lfa_set_source_rng(lfa_sim *s, int on, uint64_t rng_state, int flags) {
 	if (!s) return LFA_E_INVALID;
-	if (on && s->dist)
-		return lfa_fail(s, LFA_E_UNSUPPORTED, "fluid sources that draw from the pcg32 on a slab decomposition: the ranks' needs would "
-		                                      "have to be merged into one scan (not implemented)");
-	if (on && (flags & ~LFA_SEED_DRAW_LTR)) return lfa_fail(s, LFA_E_INVALID, "lfa_set_source_rng: flags 0 or LFA_SEED_DRAW_LTR");
+	if (on && (flags & ~(LFA_SEED_DRAW_LTR | LFA_SEED_COLLECTIVE)))
+		return lfa_fail(s, LFA_E_INVALID, "lfa_set_source_rng: flags LFA_SEED_DRAW_LTR, LFA_SEED_COLLECTIVE or none");
+	if (on && s->dist && !(flags & LFA_SEED_COLLECTIVE))
+		return lfa_fail(s, LFA_E_UNSUPPORTED, "fluid sources that draw from the pcg32 on a slab decomposition: pass LFA_SEED_COLLECTIVE "
+		                                      "(every rank then switches the mode on with the same state)");
 	s->src_rng_on = on != 0;
 	s->src_rng_state = on ? rng_state : 0;
 	s->src_rng_flags = on ? flags : 0;
+	return LFA_OK;
+}
+
+extern "C" int lfa_source_last(const lfa_sim *s, uint64_t out[3]) {
+	if (!s || !out) return LFA_E_INVALID;
+	for (int k = 0; k < 3; ++k) out[k] = s->source_last[k];
 	return LFA_OK;
 }
 
@@ -1551,7 +1678,7 @@ extern "C" int lfa_correct_collide_undo(lfa_sim *s) {
 int lfa_g2p_stale(lfa_sim *s);  // grid_ops.hip
 extern "C" int lfa_time_step(lfa_sim *s, double dt, double *residual, uint64_t *iterations) {
 	if (!s) return LFA_E_INVALID;
-	if (s->src_rng_on && s->dist)  // (before anything moves: lfa_update_sources would refuse in the middle of the step)
+	if (s->src_rng_on && s->dist && !(s->src_rng_flags & LFA_SEED_COLLECTIVE))  // (before anything moves: lfa_update_sources would refuse in the middle of the step)
 		return lfa_fail(s, LFA_E_UNSUPPORTED, "lfa_time_step: fluid sources that draw from the pcg32 (lfa_set_source_rng) on a slab decomposition");
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));

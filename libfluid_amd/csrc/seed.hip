@@ -253,6 +253,159 @@ int lfa_source_seed_rng(lfa_sim *s, const uint32_t *off, size_t base, size_t tot
 	return LFA_OK;
 }
 
+uint64_t lfa_pcg32_advance(uint64_t state, uint64_t draws) { return pcg_advance(state, draws); }
+
+// ---- slabs (LFA_SEED_COLLECTIVE). The draw number of an entry's first particle is its offset among the new particles of ALL
+// ranks in source order: lfa_update_sources has summed the ranks' needs into one vector over the job-wide entry list (one
+// all-reduce) and scanned it. A particle belongs to the rank whose tile layers hold its KEY, as in the collective lfa_seed_box;
+// only a particle of a cell next to a slab face can have its key beyond the face, so the count pass draws those entries (z alone:
+// the two coordinates it skips are one jump of four draws) and takes the need of every other entry as it stands. The write pass
+// draws like k_source_seed_rng and places the kept particles by the scan of the kept counts, numbered by their draw number.
+struct SourceSlabArgs {
+	const uint32_t *cell, *of, *gidx, *mode;  // the candidate entries (lfa_sim::SourceSlab)
+	const uint32_t *need, *first;             // per job-wide entry
+	size_t n_cand;
+	GridDims g;
+	IngestParams ip;
+	uint64_t state;
+	int nbits, ltr;
+	int slab_lo, slab_hi;  // own tile layers
+};
+
+__device__ inline uint64_t source_jump(const SourceSlabArgs &a, uint32_t first) {
+	uint64_t st = a.state;
+	const uint64_t dist = 6ull * first;
+	for (int j = 0; j < a.nbits; ++j)
+		if ((dist >> j) & 1ull) st = st * c_jump.mult[j] + c_jump.plus[j];
+	return st;
+}
+__device__ inline void source_cell_coords(const GridDims &g, uint32_t b, int (&cc)[3]) {
+	int tx, ty, tz;
+	tile_coords(g, (int)(b >> 9), tx, ty, tz);
+	const int l = (int)(b & 511);
+	cc[0] = tx * 8 + (l & 7); cc[1] = ty * 8 + ((l >> 3) & 7); cc[2] = tz * 8 + (l >> 6);
+}
+__device__ inline bool source_owned(const SourceSlabArgs &a, double z, int &cz, float &tz) {
+	cell_and_fraction(z, a.ip.off[2], a.ip.h, a.g.nz, cz, tz);
+	return (cz >> 3) >= a.slab_lo && (cz >> 3) < a.slab_hi;
+}
+
+/// Count pass, one thread per candidate entry: keep[c] = its particles whose key lies in the own tile layers.
+__global__ void __launch_bounds__(256) k_source_slab_count(SourceSlabArgs a, uint32_t *keep) {
+	const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (c >= a.n_cand) return;
+	const uint32_t gi = a.gidx[c], cnt = a.need[gi];
+	if (!cnt || !a.mode[c]) {  // (mode 0: an own cell with own cells, or the grid's end, below and above it)
+		keep[c] = cnt;
+		return;
+	}
+	uint64_t st = source_jump(a, a.first[gi]);
+	int cc[3], cz;
+	float tz;
+	source_cell_coords(a.g, a.cell[c], cc);
+	const double corner = a.ip.off[2] + (double)cc[2] * a.ip.h;
+	uint32_t k = 0;
+	for (uint32_t j = 0; j < cnt; ++j) {
+		// z is the first of the three doubles (default) or the last (LFA_SEED_DRAW_LTR); four draws are x and y
+		if (a.ltr) st = st * c_jump.mult[2] + c_jump.plus[2];
+		const double z = corner + seed_uniform(st, a.ip.h);
+		if (!a.ltr) st = st * c_jump.mult[2] + c_jump.plus[2];
+		k += source_owned(a, z, cz, tz) ? 1u : 0u;
+	}
+	keep[c] = k;
+}
+
+/// Write pass: the kept particles of candidate c become the records base + keep_off[c] .. in draw order; id = id_base + draw number.
+__global__ void __launch_bounds__(256) k_source_slab_write(SourceSlabArgs a, const uint32_t *keep, const uint32_t *keep_off,
+                                                           const float *src_vel, ParticleSoA p, size_t base, size_t kept,
+                                                           size_t total_all, uint64_t id_base, double *positions) {
+	const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (c >= a.n_cand || !keep[c]) return;
+	const uint32_t gi = a.gidx[c], cnt = a.need[gi], first = a.first[gi];
+	uint64_t st = source_jump(a, first);
+	int cc[3];
+	source_cell_coords(a.g, a.cell[c], cc);
+	const int nn[3] = {a.g.nx, a.g.ny, a.g.nz};
+	double corner[3];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) corner[k] = a.ip.off[k] + (double)cc[k] * a.ip.h;
+	const float *vel = src_vel + 3 * a.of[c];
+	const float v0 = vel[0], v1 = vel[1], v2 = vel[2];
+	size_t w = keep_off[c];
+	for (uint32_t j = 0; j < cnt; ++j) {
+		double u[3];
+		if (a.ltr) {
+			u[0] = seed_uniform(st, a.ip.h); u[1] = seed_uniform(st, a.ip.h); u[2] = seed_uniform(st, a.ip.h);
+		} else {
+			u[2] = seed_uniform(st, a.ip.h); u[1] = seed_uniform(st, a.ip.h); u[0] = seed_uniform(st, a.ip.h);
+		}
+		double x[3];
+#pragma unroll
+		for (int k = 0; k < 3; ++k) x[k] = corner[k] + u[k];
+		int ci[3];
+		float t[3];
+		if (!source_owned(a, x[2], ci[2], t[2])) continue;
+		// (cannot happen: both passes draw the same numbers; keeps a write inside the arrays regardless)
+		if (w >= kept || (size_t)first + j >= total_all) return;
+		const size_t d = base + w;
+		cell_and_fraction(x[0], a.ip.off[0], a.ip.h, nn[0], ci[0], t[0]);
+		cell_and_fraction(x[1], a.ip.off[1], a.ip.h, nn[1], ci[1], t[1]);
+		p.key[d] = blocked_index(a.g, ci[0], ci[1], ci[2]);
+#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			p.t[k][d] = t[k];
+			if (positions) positions[3 * w + k] = x[k];
+		}
+		p.v[0][d] = v0; p.v[1][d] = v1; p.v[2][d] = v2;
+#pragma unroll
+		for (int k = 0; k < 9; ++k) p.c[k][d] = 0.0f;
+		p.id[d] = (uint32_t)(id_base + (uint64_t)first + (uint64_t)j);
+		++w;
+	}
+}
+
+static SourceSlabArgs source_slab_args(lfa_sim *s, size_t total_all, uint64_t state, int ltr) {
+	const lfa_sim::SourceSlab &q = s->src_slab;
+	SourceSlabArgs a;
+	a.cell = q.cell; a.of = q.of; a.gidx = q.gidx; a.mode = q.mode;
+	a.need = q.need; a.first = q.first;
+	a.n_cand = q.n_cand;
+	a.g = s->g;
+	for (int k = 0; k < 3; ++k) a.ip.off[k] = s->prm.grid_offset[k];
+	a.ip.h = s->prm.cell_size;
+	a.state = state;
+	a.nbits = 64 - __builtin_clzll(6ull * total_all | 1ull);
+	a.ltr = ltr;
+	a.slab_lo = s->slab_lo;
+	a.slab_hi = s->slab_hi;
+	return a;
+}
+
+int lfa_source_slab_count(lfa_sim *s, size_t total_all, uint64_t state, int ltr, size_t *kept) {
+	const lfa_sim::SourceSlab &q = s->src_slab;
+	*kept = 0;
+	if (!q.n_cand) return LFA_OK;
+	hipLaunchKernelGGL(k_source_slab_count, dim3((unsigned)((q.n_cand + 255) / 256)), dim3(256), 0, s->stream,
+	                   source_slab_args(s, total_all, state, ltr), q.keep);
+	LFA_LAUNCH_CHECK(s);
+	LFA_TRY(lfa_exclusive_scan_u32(s, q.keep, q.keep_off, q.n_cand, q.keep_off + q.n_cand));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 105, q.keep_off + q.n_cand, 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	*kept = s->h_pinned[105];
+	return LFA_OK;
+}
+
+int lfa_source_slab_write(lfa_sim *s, size_t base, size_t kept, size_t total_all, uint64_t id_base, uint64_t state, int ltr,
+                          double *positions_dev) {
+	const lfa_sim::SourceSlab &q = s->src_slab;
+	if (!q.n_cand || !kept) return LFA_OK;
+	hipLaunchKernelGGL(k_source_slab_write, dim3((unsigned)((q.n_cand + 255) / 256)), dim3(256), 0, s->stream,
+	                   source_slab_args(s, total_all, state, ltr), (const uint32_t *)q.keep, (const uint32_t *)q.keep_off,
+	                   (const float *)s->src_vel, s->pb[s->cur], base, kept, total_all, id_base, positions_dev);
+	LFA_LAUNCH_CHECK(s);
+	return LFA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------- entry points
 /// simulation::world_position_to_cell_index_unclamped (src/simulation.cpp:190-197): max(g, 0) before the conversion.
 /// (Anything at or beyond 2^62 cells - far outside every grid - stops there: the conversion itself would not be defined.)
