@@ -299,7 +299,7 @@ int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded);
  * dist = uniform_real_distribution<double>(0, cell_size): six 32-bit draws of the simulation's pcg32 per particle, as libstdc++
  * takes them. New particle k of a call, counted over all cells in that order, therefore starts at draw 6 k from the state on
  * entry - k is the exclusive scan of the entries' needs that lfa_update_sources computes anyway -, so every entry jumps there and
- * draws its own particles (csrc/seed.hip: k_source_seed_rng). Inactive sources and full cells draw nothing. Velocity = (float)
+ * draws its own particles (csrc/seed.hip: k_source_write). Inactive sources and full cells draw nothing. Velocity = (float)
  * of the source's, C = 0, ids continue in draw order; the call ends with the re-binning, like lfa_update_sources.
  *   rng_state : raw pcg32 state (see lfa_seed_box) on entry; on success the state after 6 x n_seeded draws. Unchanged on failure.
  *   flags     : 0 - z gets the first pair of draws, then y, then x (g++'s right-to-left evaluation of :145) - or LFA_SEED_DRAW_LTR.

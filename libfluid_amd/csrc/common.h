@@ -329,19 +329,30 @@ __host__ __device__ inline void tile_coords(const GridDims &g, int tile, int &tx
 __host__ __device__ inline bool in_grid(const GridDims &g, int x, int y, int z) {
 	return (unsigned)x < (unsigned)g.nx && (unsigned)y < (unsigned)g.ny && (unsigned)z < (unsigned)g.nz;
 }
+/// Cell coordinates of a blocked index.
+__host__ __device__ inline void cell_coords(const GridDims &g, uint32_t b, int (&c)[3]) {
+	int tx, ty, tz;
+	tile_coords(g, (int)(b >> 9), tx, ty, tz);
+	const int l = (int)(b & 511);
+	c[0] = tx * 8 + (l & 7); c[1] = ty * 8 + ((l >> 3) & 7); c[2] = tz * 8 + (l >> 6);
+}
 /// Raw (reference, x-fastest) index of a blocked index; valid only for cells inside the real grid.
 __host__ __device__ inline uint64_t raw_from_blocked(const GridDims &g, uint32_t b) {
-	int tile = (int)(b >> 9), l = (int)(b & 511);
-	int tx, ty, tz;
-	tile_coords(g, tile, tx, ty, tz);
-	int x = tx * 8 + (l & 7), y = ty * 8 + ((l >> 3) & 7), z = tz * 8 + (l >> 6);
-	return (uint64_t)x + (uint64_t)g.nx * ((uint64_t)y + (uint64_t)g.ny * (uint64_t)z);
+	int c[3];
+	cell_coords(g, b, c);
+	return (uint64_t)c[0] + (uint64_t)g.nx * ((uint64_t)c[1] + (uint64_t)g.ny * (uint64_t)c[2]);
 }
 
 // ---------------------------------------------------------------------------------------------------- particle ingest
 struct IngestParams {
 	double off[3], h;
 };
+inline IngestParams lfa_ingest_params(const lfa_sim *s) {
+	IngestParams ip;
+	for (int k = 0; k < 3; ++k) ip.off[k] = s->prm.grid_offset[k];
+	ip.h = s->prm.cell_size;
+	return ip;
+}
 
 /// Position -> (clamped cell, in-cell fraction). The cell is computed in fp64 with a true division exactly like
 /// src/simulation.cpp:253-257 (std::max(pos,0) -> size_t cast -> min(..., size-1)), so keys are bit-exact.
@@ -365,12 +376,18 @@ __device__ inline void cell_and_fraction(double pos, double off, double h, int n
 /// and the one the frame summary and lfa_download_positions work on (frame.hip) - one function, so they agree bit for bit.
 __device__ inline void particle_world_position(const GridDims &g, const IngestParams &ip, uint32_t b, float t0, float t1, float t2,
                                                double (&x)[3]) {
-	int tile = (int)(b >> 9), l = (int)(b & 511), tx, ty, tz;
-	tile_coords(g, tile, tx, ty, tz);
-	const int c[3] = {tx * 8 + (l & 7), ty * 8 + ((l >> 3) & 7), tz * 8 + (l >> 6)};
+	int c[3];
+	cell_coords(g, b, c);
 	const float t[3] = {t0, t1, t2};
 #pragma unroll
 	for (int k = 0; k < 3; ++k) x[k] = ip.off[k] + ((double)c[k] + (double)t[k]) * ip.h;
+}
+
+/// The end of every record a seeding kernel creates: C = 0 and the id.
+__device__ inline void particle_zero_c_set_id(const ParticleSoA &p, size_t d, uint32_t id) {
+#pragma unroll
+	for (int k = 0; k < 9; ++k) p.c[k][d] = 0.0f;
+	p.id[d] = id;
 }
 
 // ---------------------------------------------------------------------------------------------------- wave helpers
@@ -479,6 +496,19 @@ template <typename T> __device__ inline T wave_max(T v) {
 
 // generic exclusive scan of uint32 (scan.hip); out may alias in. Returns total in *total_dev (device) if non-null.
 int lfa_exclusive_scan_u32(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev);
+/// Words of lfa_sim::h_pinned that the seeding and source paths read a device count back through (core.hip: lfa_scan_total;
+/// seed.hip). The other files' claims: core.hip 0, 8-10, 20-29; pcg.hip 0 upwards (the solver's state) and 4-5; mg.hip 64
+/// upwards; grid_ops.hip and core.hip 100.
+enum {
+	LFA_PIN_SOURCE_TOTAL = 96,       // lfa_update_sources: particles the own entries create
+	LFA_PIN_SEED_ACCEPTED = 97,      // lfa_seed_box / _sphere: accepted candidates of the whole job ...
+	LFA_PIN_SEED_OWNED = 98,         // ... and those of them this rank keeps
+	LFA_PIN_RESIDENT = 99,           // lfa_particles_close_holes: resident records
+	LFA_PIN_SOURCE_TOTAL_ALL = 104,  // collective lfa_update_sources_rng: particles the whole job creates ...
+	LFA_PIN_SOURCE_KEPT = 105,       // ... and those of them this rank keeps
+};
+/// The scan, its total (left in *total_dev on the device) read back through h_pinned[slot]: one synchronisation of the stream.
+int lfa_scan_total(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev, int slot, size_t *total);
 
 // stage entry points implemented per file
 int lfa_particles_alloc(lfa_sim *s, size_t n);
@@ -557,6 +587,9 @@ int lfa_dist_ensure_xbuf(lfa_sim *s, int which, size_t bytes);
 int lfa_dist_migrate(lfa_sim *s, bool vc_dead = false);
 int lfa_dist_exchange_ghost_particles(lfa_sim *s);
 int lfa_particles_reserve(lfa_sim *s, size_t n_keep, size_t n_total);
+/// Slabs, records with holes (particles handed to a neighbour since the last binning carry an invalid key): the resident ones of
+/// the n_rec records move to the front of the other buffer, whole, in storage order; the handle is left unbinned (core.hip).
+int lfa_particles_close_holes(lfa_sim *s, size_t n_rec);
 /// Orders the main stream behind a correction that lfa_correct_collide_begin has running on stream3; every entry point that
 /// touches particle arrays or the solid mask calls it first (no-op otherwise).
 int lfa_corr_join(lfa_sim *s);
@@ -571,17 +604,13 @@ inline int lfa_corr_commit(lfa_sim *s) {
 /// for ever.
 void lfa_co_gate_handle(int device, int delta);
 int lfa_sources_sync(lfa_sim *s);  // flattens `sources` to the device arrays if they changed (particles.hip)
-/// The seeding kernel of lfa_update_sources with the reference's pcg32 draws (seed.hip, beside the generator): the `total` new
-/// particles of the flattened entries (src_cell / src_of / src_need, `off` = the exclusive scan of src_need) are written to the
-/// records [base, base + total) of the current buffer; positions_dev: nullptr or room for 3 x total doubles on the device.
-/// *state_after = `state` advanced by 6 x total draws.
-int lfa_source_seed_rng(lfa_sim *s, const uint32_t *off, size_t base, size_t total, uint64_t id_base, uint64_t state, int ltr,
-                        double *positions_dev, uint64_t *state_after);
-/// The same on a slab decomposition (LFA_SEED_COLLECTIVE), for the candidate entries of lfa_sim::src_slab once `need` and `first`
-/// hold the job-wide needs and their scan. _count: keep / keep_off (and *kept = the rank's total, read back) - the particles
-/// whose KEY lies in the own tile layers. _write: those particles, at the records [base, base + kept) in draw order, numbered
-/// id_base + their draw number; positions_dev compacted alike.
-int lfa_source_slab_count(lfa_sim *s, size_t total_all, uint64_t state, int ltr, size_t *kept);
-int lfa_source_slab_write(lfa_sim *s, size_t base, size_t kept, size_t total_all, uint64_t id_base, uint64_t state, int ltr,
-                          double *positions_dev);
+/// The new particles of lfa_update_sources with the reference's pcg32 draws (seed.hip, beside the generator). A single domain:
+/// the flattened entries (src_cell / src_of / src_need and, behind it, the needs' exclusive scan); a slab decomposition
+/// (LFA_SEED_COLLECTIVE): the candidate entries of lfa_sim::src_slab once `need` and `first` hold the job-wide needs and their scan.
+/// _count (slabs only): keep / keep_off and *kept = the rank's total, read back - the particles whose KEY lies in the own tile
+/// layers. _write: the kept particles, at the records [base, base + kept) in draw order, numbered id_base + their draw number;
+/// positions_dev (nullptr or room for 3 x kept doubles on the device) compacted alike. A single domain keeps all: kept = total_all.
+int lfa_source_count(lfa_sim *s, size_t total_all, uint64_t state, int ltr, size_t *kept);
+int lfa_source_write(lfa_sim *s, size_t base, size_t kept, size_t total_all, uint64_t id_base, uint64_t state, int ltr,
+                     double *positions_dev);
 uint64_t lfa_pcg32_advance(uint64_t state, uint64_t draws);  // seed.hip: the pcg32 state after `draws` 32-bit draws

@@ -157,6 +157,14 @@ int lfa_exclusive_scan_u32(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t
 	return scan_rec(s, in, out, n, s->scan_tmp, total_dev);
 }
 
+int lfa_scan_total(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev, int slot, size_t *total) {
+	LFA_TRY(lfa_exclusive_scan_u32(s, in, out, n, total_dev));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + slot, total_dev, 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	*total = s->h_pinned[slot];
+	return LFA_OK;
+}
+
 // =============================================================================================== lifetime
 extern "C" void lfa_default_params(lfa_params *p) {
 	memset(p, 0, sizeof *p);
@@ -563,9 +571,7 @@ extern "C" int lfa_upload_particles(lfa_sim *s, const void *aos152, uint64_t n) 
 	if (n == 0) return LFA_OK;
 	LFA_TRY(lfa_ensure_io(s, n * 152));
 	LFA_HIP(s, hipMemcpyAsync(s->io_buf, aos152, n * 152, hipMemcpyHostToDevice, s->stream));
-	IngestParams ip;
-	for (int k = 0; k < 3; ++k) ip.off[k] = s->prm.grid_offset[k];
-	ip.h = s->prm.cell_size;
+	const IngestParams ip = lfa_ingest_params(s);
 	hipLaunchKernelGGL(k_ingest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const double *)s->io_buf,
 	                   (size_t)n, s->pb[0], s->g, ip, s->slab_lo, s->slab_hi);
 	LFA_LAUNCH_CHECK(s);
@@ -633,6 +639,42 @@ int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot) {
 	return LFA_OK;
 }
 
+/// Slabs, records with holes: the resident records move to their place among the resident ones (slot = exclusive scan of the
+/// valid flags), whole, in storage order.
+__global__ void __launch_bounds__(256) k_close_holes(size_t n, ParticleSoA src, ParticleSoA dst, const uint32_t *slot, size_t n_dst) {
+	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n || src.key[i] == 0xFFFFFFFFu) return;
+	const size_t d = slot[i];
+	if (d >= n_dst) return;  // (cannot happen: the caller has compared the scan's total with the resident count)
+	dst.key[d] = src.key[i];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		dst.t[k][d] = src.t[k][i];
+		dst.v[k][d] = src.v[k][i];
+	}
+#pragma unroll
+	for (int k = 0; k < 9; ++k) dst.c[k][d] = src.c[k][i];
+	dst.id[d] = src.id[i];
+}
+
+int lfa_particles_close_holes(lfa_sim *s, size_t n_rec) {
+	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream, (const uint32_t *)s->pb[s->cur].key,
+	                   n_rec, s->rank);
+	LFA_LAUNCH_CHECK(s);
+	size_t n_dst = 0;
+	LFA_TRY(lfa_scan_total(s, s->rank, s->rank, n_rec, (uint32_t *)(s->pcg_state + 5), LFA_PIN_RESIDENT, &n_dst));
+	// (unbinned, np counted the holes too - lfa_dist_migrate -: then the scan is what tells the resident count)
+	if (s->binned && n_dst != s->np) return lfa_fail(s, LFA_E_INVALID, "seeding: %u resident records but %zu expected", (uint32_t)n_dst, s->np);
+	hipLaunchKernelGGL(k_close_holes, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream, n_rec, s->pb[s->cur], s->pb[s->cur ^ 1],
+	                   (const uint32_t *)s->rank, n_dst);
+	LFA_LAUNCH_CHECK(s);
+	s->cur ^= 1;
+	s->binned = false;  // the order of the last binning is gone
+	s->np = s->np_live = n_dst;
+	s->holes = false;
+	return LFA_OK;
+}
+
 extern "C" int lfa_download_particles(lfa_sim *s, void *aos152, uint64_t n, int flags) {
 	if (!s || (!aos152 && n)) return LFA_E_INVALID;
 	LFA_HIP(s, hipSetDevice(s->device));
@@ -648,9 +690,7 @@ extern "C" int lfa_download_particles(lfa_sim *s, void *aos152, uint64_t n, int 
 	LFA_TRY(lfa_ensure_io(s, n * 152));
 	// start from the caller's records so fields the device does not own (positions unless asked) survive
 	LFA_HIP(s, hipMemcpyAsync(s->io_buf, aos152, n * 152, hipMemcpyHostToDevice, s->stream));
-	IngestParams ip;
-	for (int k = 0; k < 3; ++k) ip.off[k] = s->prm.grid_offset[k];
-	ip.h = s->prm.cell_size;
+	const IngestParams ip = lfa_ingest_params(s);
 	// (slabs with holes: the records [0, np_live) include the leavers' holes, and the arrivals sit behind ceil256(np))
 	const size_t n_rec = s->binned ? s->np_live : s->np;
 	hipLaunchKernelGGL(k_export, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s->stream, (double *)s->io_buf,
@@ -723,9 +763,7 @@ __global__ void k_seed_block(size_t n, size_t first, ParticleSoA p, GridDims g, 
 		p.t[k][j] = t[k];
 		p.v[k][j] = 0.0f;
 	}
-#pragma unroll
-	for (int k = 0; k < 9; ++k) p.c[k][j] = 0.0f;
-	p.id[j] = (uint32_t)(global_ids ? i : j);
+	particle_zero_c_set_id(p, j, (uint32_t)(global_ids ? i : j));
 }
 
 extern "C" int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_t seed) {
@@ -759,9 +797,7 @@ extern "C" int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[
 	s->system_valid = false;
 	s->unknown_count_valid = false;
 	s->cur = 0;
-	IngestParams ip;
-	for (int k = 0; k < 3; ++k) ip.off[k] = s->prm.grid_offset[k];
-	ip.h = s->prm.cell_size;
+	const IngestParams ip = lfa_ingest_params(s);
 	if (n) {
 		hipLaunchKernelGGL(k_seed_block, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, first, s->pb[0], s->g,
 		                   ip, (int)lo[0], (int)lo[1], (int)lo[2], (int)(hi[0] - lo[0]), (int)(hi[1] - lo[1]), seed, s->dist ? 1 : 0);

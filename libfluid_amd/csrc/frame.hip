@@ -216,11 +216,8 @@ extern "C" int lfa_frame_stats(lfa_sim *s, struct lfa_frame_stats *out, uint32_t
 		if (!e) LFA_HIP(s, hipEventCreate(&e));
 	if (occupation) LFA_TRY(lfa_ensure_io(s, s->nc * 4));
 	FrameParams q;
-	for (int k = 0; k < 3; ++k) {
-		q.ip.off[k] = s->prm.grid_offset[k];
-		q.g[k] = s->prm.gravity[k];
-	}
-	q.ip.h = s->prm.cell_size;
+	q.ip = lfa_ingest_params(s);
+	for (int k = 0; k < 3; ++k) q.g[k] = s->prm.gravity[k];
 	// (slabs with holes: the records [0, np_live) include the leavers' holes - skipped by their key)
 	const size_t n_rec = s->binned ? s->np_live : s->np;
 	size_t blocks = (n_rec + 255) / 256;
@@ -283,9 +280,7 @@ extern "C" int lfa_download_positions(lfa_sim *s, double *xyz, uint64_t n) {
 	const uint32_t *slot = nullptr;
 	LFA_TRY(lfa_slab_download_slots(s, &slot));
 	LFA_TRY(lfa_ensure_io(s, n * 24));
-	IngestParams ip;
-	for (int k = 0; k < 3; ++k) ip.off[k] = s->prm.grid_offset[k];
-	ip.h = s->prm.cell_size;
+	const IngestParams ip = lfa_ingest_params(s);
 	const size_t n_rec = s->binned ? s->np_live : s->np;
 	const ParticleSoA &p = s->pb[s->cur];
 	hipLaunchKernelGGL(k_export_positions, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s->stream, (double *)s->io_buf, n_rec,

@@ -988,9 +988,7 @@ __global__ void k_source_seed(const uint32_t *cell, const uint32_t *src_of, cons
 			p.t[a][d] = t;
 			p.v[a][d] = vel[a];
 		}
-#pragma unroll
-		for (int k = 0; k < 9; ++k) p.c[k][d] = 0.0f;
-		p.id[d] = (uint32_t)(id_base + (uint64_t)(d - base));
+		particle_zero_c_set_id(p, d, (uint32_t)(id_base + (uint64_t)(d - base)));
 	}
 }
 }  // namespace
@@ -1151,6 +1149,56 @@ int lfa_sources_sync(lfa_sim *s) {
 	return LFA_OK;
 }
 
+/// The own entries' needs (k_source_need) into src_need.
+static int source_needs(lfa_sim *s) {
+	const size_t n = s->n_src_entries;
+	hipLaunchKernelGGL(k_source_need, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
+	                   (const uint32_t *)s->src_lo, (const uint32_t *)s->src_target, n, (const uint32_t *)s->cell_count,
+	                   (const uint32_t *)s->tile_flag, s->src_need);
+	LFA_LAUNCH_CHECK(s);
+	return LFA_OK;
+}
+
+/// Room for `count` new records behind the `base` live ones (a deferred binning is completed first: the new particles bring their
+/// own v / C), C = 0 in the home array for the ids [id_lo, id_lo + id_n) - the array sized for the ids below id_end -, and, when the
+/// caller wants the positions, its buffer checked against `count` and the device's made ready. Nothing of the handle's state moves.
+static int source_room(lfa_sim *s, size_t base, size_t count, uint64_t id_lo, size_t id_n, size_t id_end, const double *positions,
+                       uint64_t positions_capacity, const char *keeps) {
+	if (base + count >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
+	if (positions && positions_capacity < count)
+		return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: room for %llu positions but %s%zu particles",
+		                (unsigned long long)positions_capacity, keeps, count);
+	if (positions) LFA_TRY(lfa_ensure_io(s, count * 24));
+	LFA_TRY(lfa_particles_materialize(s));
+	LFA_TRY(lfa_particles_reserve(s, base, base + count));  // keeps the live records
+	if (s->c_home_valid) {
+		LFA_TRY(lfa_c_home_ensure(s, id_end));
+		for (int k = 0; k < 9 && id_n; ++k)
+			LFA_HIP(s, hipMemsetAsync(s->c_home + (size_t)k * s->c_home_cap + id_lo, 0, id_n * 4, s->stream));
+	}
+	return LFA_OK;
+}
+
+/// The `kept` new records are written behind `base`: counts, flags and the re-binning (the reference re-hashes after seeding,
+/// src/simulation.cpp:64). A call that drew from the pcg32 (rng_state) then - and only after a successful re-binning - moves the
+/// state on by the draws of the whole job's total_all particles and records lfa_source_last.
+static int source_finish(lfa_sim *s, size_t base, size_t kept, uint64_t total_all, uint64_t id_base, uint64_t *n_seeded,
+                         uint64_t *rng_state, const double *positions) {
+	s->np_live = base + kept;
+	s->np = s->np_live;
+	s->vmax2_valid = false;  // the new particles carry their source's velocity
+	if (n_seeded) *n_seeded = kept;
+	const int rc = lfa_hash_particles(s);
+	if (rc >= 0 && rng_state) {
+		if (positions) LFA_HIP(s, hipStreamSynchronize(s->stream));
+		*rng_state = lfa_pcg32_advance(*rng_state, 6ull * total_all);
+		s->source_last[0] = total_all;
+		s->source_last[1] = kept;
+		s->source_last[2] = id_base;
+	}
+	return rc;
+}
+
 /// lfa_update_sources_rng with LFA_SEED_COLLECTIVE on a slab decomposition (the checks of update_sources are done, the entry lists
 /// are current). ONE transport call - the all-reduce of the needs over the job-wide entry list -, none when no source lists an
 /// active entry; the re-binning that ends the call has its own.
@@ -1163,9 +1211,7 @@ static int update_sources_collective(lfa_sim *s, uint64_t *n_seeded, uint64_t *r
 	if (!ng) return LFA_OK;  // no entry anywhere: nothing to create, no draw, no message
 	LFA_HIP(s, hipMemsetAsync(q.need_f, 0, ng * 4, s->stream));
 	if (n) {
-		hipLaunchKernelGGL(k_source_need, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
-		                   (const uint32_t *)s->src_lo, (const uint32_t *)s->src_target, n, (const uint32_t *)s->cell_count,
-		                   (const uint32_t *)s->tile_flag, s->src_need);
+		LFA_TRY(source_needs(s));
 		hipLaunchKernelGGL(k_source_need_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream,
 		                   (const uint32_t *)s->src_need, (const uint32_t *)q.own_gidx, n, q.need_f);
 		LFA_LAUNCH_CHECK(s);
@@ -1174,10 +1220,8 @@ static int update_sources_collective(lfa_sim *s, uint64_t *n_seeded, uint64_t *r
 	hipLaunchKernelGGL(k_source_need_gather, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s->stream, (const float *)q.need_f, ng,
 	                   q.need);
 	LFA_LAUNCH_CHECK(s);
-	LFA_TRY(lfa_exclusive_scan_u32(s, q.need, q.first, ng, q.first + ng));
-	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 104, q.first + ng, 4, hipMemcpyDeviceToHost, s->stream));
-	LFA_HIP(s, hipStreamSynchronize(s->stream));
-	const size_t total_all = s->h_pinned[104];
+	size_t total_all = 0;
+	LFA_TRY(lfa_scan_total(s, q.need, q.first, ng, q.first + ng, LFA_PIN_SOURCE_TOTAL_ALL, &total_all));
 	// ---- what the job-wide count decides: every rank decides alike
 	if (!total_all) return LFA_OK;  // every source cell of the job is full: no draw, the binning stands
 	if (id_base + total_all >= ((uint64_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
@@ -1185,20 +1229,10 @@ static int update_sources_collective(lfa_sim *s, uint64_t *n_seeded, uint64_t *r
 	size_t kept = 0;
 	const size_t base = s->np_live;
 	auto seed = [&]() -> int {
-		LFA_TRY(lfa_source_slab_count(s, total_all, state, ltr, &kept));
-		if (base + kept >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
-		if (positions && positions_capacity < kept)
-			return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: room for %llu positions but this rank keeps %zu particles",
-			                (unsigned long long)positions_capacity, kept);
-		if (positions) LFA_TRY(lfa_ensure_io(s, kept * 24));
-		LFA_TRY(lfa_particles_materialize(s));
-		LFA_TRY(lfa_particles_reserve(s, base, base + kept));
-		if (s->c_home_valid) {  // C = 0 for every new id of the job: the ids a rank keeps are no contiguous range
-			LFA_TRY(lfa_c_home_ensure(s, (size_t)(id_base + total_all)));
-			for (int k = 0; k < 9; ++k)
-				LFA_HIP(s, hipMemsetAsync(s->c_home + (size_t)k * s->c_home_cap + id_base, 0, total_all * 4, s->stream));
-		}
-		LFA_TRY(lfa_source_slab_write(s, base, kept, total_all, id_base, state, ltr, positions ? (double *)s->io_buf : (double *)nullptr));
+		LFA_TRY(lfa_source_count(s, total_all, state, ltr, &kept));
+		// (C = 0 for every new id of the job: the ids a rank keeps are no contiguous range)
+		LFA_TRY(source_room(s, base, kept, id_base, total_all, (size_t)(id_base + total_all), positions, positions_capacity, "this rank keeps "));
+		LFA_TRY(lfa_source_write(s, base, kept, total_all, id_base, state, ltr, positions ? (double *)s->io_buf : (double *)nullptr));
 		if (positions && kept) LFA_HIP(s, hipMemcpyAsync(positions, s->io_buf, kept * 24, hipMemcpyDeviceToHost, s->stream));
 		return LFA_OK;
 	};
@@ -1208,23 +1242,11 @@ static int update_sources_collective(lfa_sim *s, uint64_t *n_seeded, uint64_t *r
 		return rc_seed;
 	}
 	s->next_global_id = id_base + total_all;
-	s->np_live = base + kept;
-	s->np = s->np_live;
-	s->vmax2_valid = false;
-	if (n_seeded) *n_seeded = kept;
-	const int rc = lfa_hash_particles(s);
-	if (rc >= 0) {
-		if (positions) LFA_HIP(s, hipStreamSynchronize(s->stream));
-		*rng_state = lfa_pcg32_advance(state, 6ull * total_all);
-		s->source_last[0] = total_all;
-		s->source_last[1] = kept;
-		s->source_last[2] = id_base;
-	}
-	return rc;
+	return source_finish(s, base, kept, total_all, id_base, n_seeded, rng_state, positions);
 }
 
 /// lfa_update_sources. rng_state == nullptr: positions from the counter-based generator (k_source_seed); else the reference's
-/// draws from the pcg32 in *rng_state (seed.hip: k_source_seed_rng; slabs: update_sources_collective), advanced on success.
+/// draws from the pcg32 in *rng_state (seed.hip: k_source_write; slabs: update_sources_collective), advanced on success.
 static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, int flags, double *positions, uint64_t positions_capacity) {
 	if (n_seeded) *n_seeded = 0;
 	if (rng_state) {
@@ -1245,15 +1267,9 @@ static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, i
 	size_t total = 0;
 	uint32_t *off = s->src_need ? s->src_need + s->src_cap + 1 : nullptr;
 	if (n) {
-		hipLaunchKernelGGL(k_source_need, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
-		                   (const uint32_t *)s->src_lo, (const uint32_t *)s->src_target, n, (const uint32_t *)s->cell_count,
-		                   (const uint32_t *)s->tile_flag, s->src_need);
-		LFA_LAUNCH_CHECK(s);
+		LFA_TRY(source_needs(s));
 		// exclusive scan into the second half of the scratch; the total is read back (the host has to size the particle arrays)
-		LFA_TRY(lfa_exclusive_scan_u32(s, s->src_need, off, n, off + n));
-		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 96, off + n, 4, hipMemcpyDeviceToHost, s->stream));
-		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		total = s->h_pinned[96];
+		LFA_TRY(lfa_scan_total(s, s->src_need, off, n, off + n, LFA_PIN_SOURCE_TOTAL, &total));
 	}
 	// slabs: what every rank creates, gathered (one sum all-reduce of a vector with one slot per rank) - the ids of the new
 	// particles continue the job-wide numbering in rank order, and either every rank re-bins or none does
@@ -1277,45 +1293,23 @@ static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, i
 		s->next_global_id += total_all;
 	}
 	if (!total_all) return LFA_OK;  // every source cell is full: the binning stands
-	if (s->np_live + total >= ((size_t)1 << 32)) return lfa_fail(s, LFA_E_INVALID, "more than 2^32 particles");
-	if (rng_state && positions && positions_capacity < total)
-		return lfa_fail(s, LFA_E_INVALID, "lfa_update_sources_rng: room for %llu positions but %zu particles",
-		                (unsigned long long)positions_capacity, total);
-	if (rng_state && positions) LFA_TRY(lfa_ensure_io(s, total * 24));
 	const size_t base = s->np_live;
-	LFA_TRY(lfa_particles_materialize(s));  // the new particles bring their own v / C: a deferred binning is completed first
-	LFA_TRY(lfa_particles_reserve(s, base, base + total));  // keeps the live records
-	if (s->c_home_valid) {  // the new particles get the ids id_base .. id_base + total - 1 (single domain: = base) and C = 0
-		LFA_TRY(lfa_c_home_ensure(s, s->dist ? (size_t)s->next_global_id : base + total));
-		for (int k = 0; k < 9 && total; ++k)
-			LFA_HIP(s, hipMemsetAsync(s->c_home + (size_t)k * s->c_home_cap + id_base, 0, total * 4, s->stream));
-	}
-	uint64_t state_after = 0;
+	// the new particles get the ids id_base .. id_base + total - 1 (single domain: = base)
+	LFA_TRY(source_room(s, base, total, id_base, total, s->dist ? (size_t)s->next_global_id : base + total, positions, positions_capacity, ""));
 	if (rng_state) {
-		LFA_TRY(lfa_source_seed_rng(s, off, base, total, id_base, *rng_state, (flags & LFA_SEED_DRAW_LTR) ? 1 : 0,
-		                            positions ? (double *)s->io_buf : (double *)nullptr, &state_after));
+		LFA_TRY(lfa_source_write(s, base, total, total, id_base, *rng_state, (flags & LFA_SEED_DRAW_LTR) ? 1 : 0,
+		                         positions ? (double *)s->io_buf : (double *)nullptr));
 		if (positions) LFA_HIP(s, hipMemcpyAsync(positions, s->io_buf, total * 24, hipMemcpyDeviceToHost, s->stream));
 	} else {
 		++s->source_epoch;
+		if (total) {
+			hipLaunchKernelGGL(k_source_seed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
+			                   (const uint32_t *)s->src_of, (const uint32_t *)s->src_need, (const uint32_t *)off, n, (const float *)s->src_vel,
+			                   s->pb[s->cur], base, 0x5EED50ull + s->source_epoch * 0x632BE59BD9B4E019ull, id_base);
+			LFA_LAUNCH_CHECK(s);
+		}
 	}
-	if (total && !rng_state) {
-		hipLaunchKernelGGL(k_source_seed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->src_cell,
-		                   (const uint32_t *)s->src_of, (const uint32_t *)s->src_need, (const uint32_t *)off, n, (const float *)s->src_vel,
-		                   s->pb[s->cur], base, 0x5EED50ull + s->source_epoch * 0x632BE59BD9B4E019ull, id_base);
-		LFA_LAUNCH_CHECK(s);
-	}
-	s->np_live = base + total;
-	s->np = s->np_live;
-	s->vmax2_valid = false;  // the new particles carry their source's velocity
-	if (n_seeded) *n_seeded = total;
-	const int rc = lfa_hash_particles(s);  // the reference re-hashes after seeding (src/simulation.cpp:64)
-	if (rc >= 0 && rng_state) {
-		if (positions) LFA_HIP(s, hipStreamSynchronize(s->stream));
-		*rng_state = state_after;
-		s->source_last[0] = s->source_last[1] = total;
-		s->source_last[2] = id_base;
-	}
-	return rc;
+	return source_finish(s, base, total, total_all, id_base, n_seeded, rng_state, positions);
 }
 
 extern "C" int lfa_update_sources(lfa_sim *s, uint64_t *n_seeded) {

@@ -116,3 +116,38 @@ def sorted_rows(pos, *more):
 def raw_index(grid, cells):
     nx, ny, _ = grid["size"]
     return (cells[:, 0] + nx * (cells[:, 1] + ny * cells[:, 2])).astype(np.uint64)
+
+
+# ---- the counter-based default of lfa_update_sources (tests/source_model.py: counter_update_sources)
+COUNTER_GRID = dict(size=(16, 16, 16), cell_size=0.25, offset=(-1.3, 0.7, 1e-3))
+# (3,3,3) under root 2, then root 3: 6, then 19 - and 19 again in every later call; an inactive source in between
+COUNTER_SOURCES = [([(3, 3, 3), (5, 9, 12)], (1.0, 0.1, -0.5), 2, True),
+                   ([(7, 7, 7), (3, 3, 3)], (9.0, 9.0, 9.0), 3, False),
+                   ([(3, 3, 3), (12, 2, 8), (4, 4, 6)], (0.0, 2.5, 0.3), 3, True)]
+
+
+def counter_parts():
+    """Three resident particles at cell centres: two in the source cell (3,3,3), one in (12,2,8)."""
+    parts = np.zeros(3, dtype=scenes.PARTICLE_DTYPE)
+    cells = np.array([(3, 3, 3), (12, 2, 8), (3, 3, 3)], dtype=np.float64)
+    parts["pos"] = np.asarray(COUNTER_GRID["offset"]) + (cells + 0.5) * COUNTER_GRID["cell_size"]
+    parts["old_pos"] = parts["pos"]
+    parts["vel"] = [(0.5, -1.0, 2.0), (0.0, 0.25, 0.0), (-3.0, 0.0, 1.0)]
+    return parts
+
+
+def counter_expected(n_calls, ranks_z=(None,)):
+    """Per call: per rank (records, ids) of counter_update_sources, ids continuing in rank order from the resident particles'."""
+    g = COUNTER_GRID
+    counts = srcm.cell_counts(g["size"], g["cell_size"], g["offset"], counter_parts()["pos"])
+    next_id, calls = 3, []
+    for epoch in range(1, n_calls + 1):
+        per_rank = []
+        for zr in ranks_z:
+            rec, ids = srcm.counter_update_sources(g["size"], g["cell_size"], g["offset"], counts, COUNTER_SOURCES, epoch, next_id, zr)
+            next_id += len(rec)
+            per_rank.append((rec, ids))
+        for rec, _ in per_rank:
+            counts = counts + np.bincount(rec["raw"].astype(np.int64), minlength=counts.size)
+        calls.append(per_rank)
+    return calls

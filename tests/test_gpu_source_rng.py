@@ -214,3 +214,25 @@ def test_mode_off_is_the_default_path():
         plain.hash(); toggled.hash()
     assert np.array_equal(plain.particle_ids(), toggled.particle_ids())
     plain.close(); toggled.close()
+
+
+def test_counter_based_default_against_the_model():
+    """K: the plain lfa_update_sources (no pcg32) creates the records of source_model.counter_update_sources, byte for byte, in
+    two consecutive calls (the epoch advances); the resident records stay what they were."""
+    grid = sc.COUNTER_GRID
+    sim = lfa.Sim(**grid)
+    sim.upload_particles(sc.counter_parts())
+    sim.hash()
+    for cells, vel, root, active in sc.COUNTER_SOURCES:
+        sim.add_source(cells, vel, root, active, False)
+    held = sim.download_particles(write_positions=True)
+    for (want, ids), n_want in zip((c[0] for c in sc.counter_expected(2)), (86, 19)):
+        assert len(want) == n_want
+        assert sim.update_sources() == n_want
+        got = sim.download_particles(write_positions=True)  # (single domain: record i is particle i)
+        assert np.array_equal(sim.particle_ids(), np.arange(len(held) + n_want))
+        assert np.array_equal(ids, np.arange(len(held), len(held) + n_want))
+        assert got[:len(held)].tobytes() == held.tobytes()
+        assert got[len(held):].tobytes() == want.tobytes()
+        held = got
+    sim.close()

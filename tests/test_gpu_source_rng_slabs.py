@@ -266,3 +266,24 @@ def test_counter_based_default_is_untouched():
             assert b.source_last() == (0, 0, 0)
     close_all(hub_a, plain)
     close_all(hub_b, toggled)
+
+
+def test_counter_based_default_against_the_model():
+    """Plain update_sources on two slabs: every rank creates the model's records of its own cell layers, the ids continue in rank
+    order; gathered by id they are the model's with id_base per rank, byte for byte, in two consecutive calls."""
+    from tests import source_cases as sc
+    hub, sims = make_slabs(sc.COUNTER_GRID, [0, 1, 2], sc.counter_parts(), sc.COUNTER_SOURCES)
+    try:
+        held, held_ids = gather(sims)
+        assert np.array_equal(held_ids, np.arange(3))
+        for per_rank, n_want in zip(sc.counter_expected(2, ranks_z=((0, 8), (8, 16))), ((52, 34), (19, 0))):
+            assert tuple(len(rec) for rec, _ in per_rank) == n_want
+            assert tuple(collective(sims, lambda r, s: s.update_sources())) == n_want
+            got, ids = gather(sims)
+            want = np.concatenate([held] + [rec for rec, _ in per_rank])
+            assert np.array_equal(ids, np.concatenate([held_ids] + [i for _, i in per_rank]))
+            assert np.array_equal(ids, np.arange(len(want)))
+            assert got.tobytes() == want.tobytes()
+            held, held_ids = got, ids
+    finally:
+        close_all(hub, sims)
