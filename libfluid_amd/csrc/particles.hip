@@ -314,13 +314,16 @@ __device__ inline float4 fine_record(int lx, int ly, int lz, float t0, float t1,
 	const uint32_t b2 = (__float_as_uint(t2) & 0x3FFFFFFFu) | ((uint32_t)(lz & 1) << 31);
 	return make_float4(__uint_as_float(b0), __uint_as_float(b1), __uint_as_float(b2), __uint_as_float(index));
 }
-__device__ inline void fine_decode(const float4 &r, int fy, int fz, float t[3], int l[3]) {
+/// (y0, z0: the first cell the fine row overlaps, floor(8 f / 11))
+__device__ inline void fine_decode_at(const float4 &r, int y0, int z0, float t[3], int l[3]) {
 	const uint32_t b0 = __float_as_uint(r.x), b1 = __float_as_uint(r.y), b2 = __float_as_uint(r.z);
 	t[0] = __uint_as_float(b0 & 0x3FFFFFFFu); t[1] = __uint_as_float(b1 & 0x3FFFFFFFu); t[2] = __uint_as_float(b2 & 0x3FFFFFFFu);
 	l[0] = (int)(b0 >> 30) | ((int)(b1 >> 31) << 2);
-	const int y0 = (8 * fy) / FT, z0 = (8 * fz) / FT;
 	l[1] = y0 + ((y0 ^ (int)(b1 >> 30)) & 1);
 	l[2] = z0 + ((z0 ^ (int)(b2 >> 31)) & 1);
+}
+__device__ inline void fine_decode(const float4 &r, int fy, int fz, float t[3], int l[3]) {
+	fine_decode_at(r, (8 * fy) / FT, (8 * fz) / FT, t, l);
 }
 
 /// Per particle tile: its particles grouped by fine cell - fine_start[tile][f] = first record of fine cell f (absolute), records
@@ -556,6 +559,9 @@ __device__ unsigned long long g_corr_prof[8];
 #else
 #define CORR_STAMP(k) do { } while (0)
 #endif
+// (Budget, both instantiations: <= 128 VGPRs - the 4 waves per SIMD asked for below -, no scratch, static LDS <= 81 920 B for the
+// first pass (two workgroups per CU) and <= 163 840 B for the second. The compiler spills silently beyond 128:
+// tests/test_kernel_budgets.py reads the figures from the compiler's metadata.)
 template <int CAP, bool ONLY>
 __global__ void __launch_bounds__(ONLY ? CORR_THREADS_BIG : CORR_THREADS, 4)
 k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx, float *out_ty, float *out_tz, GridDims g,
@@ -566,7 +572,13 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 	__shared__ float px[CAP], py[CAP], pz[CAP];
 	__shared__ uint32_t fcnt[CNT];          // particles per block fine cell; afterwards the own list (u16)
 	__shared__ uint16_t foff[FB_N + 1];        // first staged slot of every block fine cell
-	__shared__ uint32_t rowsrc[FB_ROWS * 3];   // first source record of the three runs of a fine row (x-1 tile, own x tile, x+1 tile)
+	// Per fine row of the block, everything the staging derives from the row alone (8 words, read as two 128-bit halves):
+	// [0..2] source record of staged slot s in the row's three runs (x-1 tile, own x tile, x+1 tile) is base[seg] + s
+	// [3]    first slot of the own x run | first slot of the x+1 run << 16
+	// [4..5] 8 dy, 8 dz: the source tile's offset in cells     [6] y0 | z0 << 8: first cell of the fine row (fine_decode)
+	// [7]    own list: a slot s of the own x run is entry [7] + s; ROW_NOT_OWN: the row is not listed
+	__shared__ __attribute__((aligned(16))) uint32_t rowd[FB_ROWS * 8];
+	constexpr uint32_t ROW_NOT_OWN = 0x80000000u;  // (a listed base is within +- CAP)
 	__shared__ uint32_t ownoff[FT * FT_PL + 1];
 	__shared__ int srct[27];                   // the source tiles around the own one
 	__shared__ uint32_t wsum[T / 64];
@@ -590,6 +602,9 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 		const int nzb = own_n + 2;   // block layers
 		const int nrows = FB * nzb, nown_rows = FT * (nzb - 2);
 		const bool open_water = (tile_clear[tile] & 1) != 0;  // no solid cell within a tile of this one
+		// every cell c of the tile has c - 7 >= 1 and c + 7 <= n - 2 on all three axes, and collisions are on in open water (uniform)
+		const bool lean = open_water && mp.collide && tx >= 1 && ty >= 1 && tz >= 1 && 8 * tx + 16 <= g.nx && 8 * ty + 16 <= g.ny &&
+		                  8 * tz + 16 <= g.nz;
 		__syncthreads();
 #ifdef CORR_PROFILE
 		unsigned long long stamp_ = wall_clock64();
@@ -597,15 +612,21 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 #endif
 		// ---- the 27 source tiles (-1: outside the grid or without particles), then the block's fine cells: where their records
 		// are, how many
-		if (threadIdx.x < 27) {
+		// (the thread index behind an empty asm: what the first few threads derive from it - the source tiles, the row descriptors -
+		// is a handful of instructions per work item; hoisted out of the work-item loop it would occupy registers across the
+		// pair walk)
+		uint32_t tid = threadIdx.x;
+		asm volatile("" : "+v"(tid));
+		if (tid < 27) {
 			int fx, fy, fz;
-			srct[threadIdx.x] = fine_source(g, tile_count, tx, ty, tz, FT * ((int)threadIdx.x % 3 - 1), FT * (((int)threadIdx.x / 3) % 3 - 1),
-			                                FT * ((int)threadIdx.x / 9 - 1), fx, fy, fz);
+			srct[tid] = fine_source(g, tile_count, tx, ty, tz, FT * ((int)tid % 3 - 1), FT * (((int)tid / 3) % 3 - 1), FT * ((int)tid / 9 - 1), fx,
+			                        fy, fz);
 		}
 		__syncthreads();
 #pragma unroll
 		for (int k = 0; k < PER; ++k) {
-			const int f = threadIdx.x + T * k;
+			// (the last round's cell coordinates are worked out per work item, not kept in registers across the loop: see `tid`)
+			const int f = (int)(k == PER - 1 ? tid : threadIdx.x) + T * k;
 			uint32_t cnt = 0, src0 = 0;
 			if (f < FB * nrows) {
 				const int bx = f % FB, row = f / FB, by = row % FB, bz = row / FB;
@@ -618,7 +639,7 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 					src0 = fs[0];
 					cnt = fs[1] - src0;
 				}
-				if (bx <= 1 || bx == FB - 1) rowsrc[row * 3 + (bx <= 1 ? bx : 2)] = src0;
+				if (bx <= 1 || bx == FB - 1) rowd[row * 8 + (bx <= 1 ? bx : 2)] = src0;  // (biased by the run's first slot below)
 			}
 			fcnt[f] = cnt;
 		}
@@ -661,11 +682,11 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 		}
 		__syncthreads();
 		// ---- own particles: the middle runs of the rows by = 1 .. FT, bz = 1 .. nzb - 2; their lengths, scanned by the first waves
-		uint32_t own_total = 0;
+		uint32_t own_total = 0, own_first = 0;  // own_first: list entry of the first own particle of this thread's own row
 		{
 			uint32_t len = 0;
-			if (threadIdx.x < (unsigned)nown_rows) {
-				const int row = (1 + threadIdx.x % FT) + FB * (1 + threadIdx.x / FT);
+			if (tid < (unsigned)nown_rows) {
+				const int row = (1 + (int)tid % FT) + FB * (1 + (int)tid / FT);
 				len = (uint32_t)foff[row * FB + FB - 1] - (uint32_t)foff[row * FB + 1];
 			}
 			uint32_t in2 = len;
@@ -681,70 +702,96 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 				if (w < wid) wo += wsum[w];
 				own_total += wsum[w];
 			}
-			if (threadIdx.x < (unsigned)nown_rows) ownoff[threadIdx.x] = wo + in2 - len;
-			if (threadIdx.x == 0) ownoff[nown_rows] = own_total;
+			own_first = wo + in2 - len;
+			if (tid < (unsigned)nown_rows) ownoff[tid] = own_first;
+			if (tid == 0) ownoff[nown_rows] = own_total;
 		}
 		// (a crowded part with more own particles than the list holds - it lives in the count array - finds them through the row
 		// offsets instead: uniform)
 		const bool listed = own_total <= 2u * CNT;
+		// ---- the row descriptors: thread r writes row r's, thread t the own-list base of the t-th own row
+		if (tid < (unsigned)nrows) {
+			const int r = (int)tid, by = r % FB, bz = r / FB;
+			const int gy = by - 1, gz = gz0 + bz;
+			const int dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0), dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
+			const int fy = gy - FT * dy, fz = gz - FT * dz;
+			const uint32_t d0 = foff[r * FB], d1 = foff[r * FB + 1], d2 = foff[r * FB + FB - 1];
+			uint32_t *rd = rowd + r * 8;
+			rd[0] -= d0; rd[1] -= d1; rd[2] -= d2;
+			rd[3] = d1 | (d2 << 16);
+			rd[4] = (uint32_t)(8 * dy); rd[5] = (uint32_t)(8 * dz);
+			rd[6] = (uint32_t)((8 * fy) / FT) | ((uint32_t)((8 * fz) / FT) << 8);
+			if (!(listed && by >= 1 && by <= FT && bz >= 1 && bz <= nzb - 2)) rd[7] = ROW_NOT_OWN;
+		}
+		if (listed && tid < (unsigned)nown_rows) {
+			const int row = (1 + (int)tid % FT) + FB * (1 + (int)tid / FT);
+			rowd[row * 8 + 7] = own_first - (uint32_t)foff[row * FB + 1];
+		}
 		__syncthreads();  // (every count has been read: `own` may overwrite the array)
 		CORR_STAMP(0);  // counts, scans, own offsets
-		// ---- stage the rows: a wave per fine row copies its three runs - one cell of the x-1 tile, the own x tile's eleven, one
-		// of the x+1 tile - which follow each other in the block (positions relative to the own tile's origin, in cells)
-		// Flat: a thread per staged SLOT, its row found by a seven-step search over the rows' first slots - every thread's record
-		// load is issued at once, two per thread in flight. (Round 5 and before: a wave per fine row, one row after the other - 13
-		// dependent HBM round trips per wave and work item. Measured, round 6: C4 4.91 -> 4.84 ms, the late C3 sheet 2.07 -> 1.89;
-		// 2, 4 or 8 records in flight make no difference - the kernel is bound by its instruction count, not by this latency.)
+		// ---- stage the rows: their three runs - one cell of the x-1 tile, the own x tile's eleven, one of the x+1 tile - follow
+		// each other in the block (positions relative to the own tile's origin, in cells)
+		// Flat: a thread per staged SLOT - every thread's record load is issued at once, CORR_STAGE_DEPTH per thread in flight.
+		// (Round 5 and before: a wave per fine row, one row after the other - 13 dependent HBM round trips per wave and work
+		// item. Measured, round 6: C4 4.91 -> 4.84 ms, the late C3 sheet 2.07 -> 1.89; 2, 4 or 8 records in flight make no
+		// difference - the kernel is bound by its instruction count, not by this latency.)
+		// A slot's row: the 64 slots of a wave are consecutive, so the rows of its first and last slot come from ballots over
+		// the rows' first slots (lane l holds those of rows l and l + 64; they are monotone: a population count is a row), and
+		// a lane searches between the two only - no step inside a long row, one or two in a dense block. Rows can be empty,
+		// several in a row: the search takes the last row that starts at or before the slot, which is the one that holds it.
 		{
-			auto locate = [&](uint32_t slot, uint32_t &src, int &seg, int &dy, int &dz, int &fy, int &fz, int &ownslot) {
-				int r = 0;
-#pragma unroll
-				for (int step = 64; step; step >>= 1) {
-					const int c = r + step;
-					if (c < nrows && (uint32_t)foff[c * FB] <= slot) r = c;
-				}
-				const int by = r % FB, bz = r / FB;
-				const int gy = by - 1, gz = gz0 + bz;
-				dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0); dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
-				fy = gy - FT * dy; fz = gz - FT * dz;
-				const uint32_t d0 = foff[r * FB], d1 = foff[r * FB + 1], d2 = foff[r * FB + FB - 1];
-				seg = slot < d1 ? 0 : (slot < d2 ? 1 : 2);
-				src = rowsrc[r * 3 + seg] + (slot - (seg == 0 ? d0 : (seg == 1 ? d1 : d2)));
-				// the own list: slot order = fine-cell order
-				ownslot = (listed && seg == 1 && by >= 1 && by <= FT && bz >= 1 && bz <= nzb - 2)
-				              ? (int)(ownoff[(by - 1) + FT * (bz - 1)] + (slot - d1)) : -1;
+			static_assert(FB_ROWS <= 128, "two row starts per lane");
+			const int rl = (int)(tid & 63u);
+			const uint32_t rs_lo = rl < nrows ? (uint32_t)foff[rl * FB] : 0xFFFFFFFFu;
+			const uint32_t rs_hi = rl + 64 < nrows ? (uint32_t)foff[(rl + 64) * FB] : 0xFFFFFFFFu;
+			auto row_of = [&](uint32_t s) -> int {  // (every lane of the wave calls it, s uniform)
+				return (int)__popcll(__ballot(rs_lo <= s)) + (int)__popcll(__ballot(rs_hi <= s)) - 1;
 			};
-			auto put = [&](uint32_t slot, const float4 &rec, int seg, int dy, int dz, int fy, int fz, int ownslot) {
+			auto locate = [&](uint32_t slot, int r_first, int r_last, uint32_t &src, int &rs) {
+				int r = r_first;
+				const int span = r_last - r_first;  // (uniform)
+				for (int step = span ? 1 << (31 - __builtin_clz(span)) : 0; step; step >>= 1) {
+					const int c = r + step;
+					if (c <= r_last && (uint32_t)foff[c * FB] <= slot) r = c;
+				}
+				const uint4 d = *(const uint4 *)(rowd + r * 8);
+				const int seg = slot < (d.w & 0xFFFFu) ? 0 : (slot < (d.w >> 16) ? 1 : 2);
+				src = (seg == 0 ? d.x : (seg == 1 ? d.y : d.z)) + slot;
+				rs = r | (seg << 8);
+			};
+			auto put = [&](uint32_t slot, const float4 &rec, int rs) {
+				const int r = rs & 255, seg = rs >> 8;
+				const uint4 d = *(const uint4 *)(rowd + r * 8 + 4);
 				float t[3];
 				int l[3];
-				fine_decode(rec, fy, fz, t, l);
+				fine_decode_at(rec, (int)(d.z & 255u), (int)(d.z >> 8), t, l);
 				px[slot] = (float)(8 * (seg - 1) + l[0]) + t[0];
-				py[slot] = (float)(8 * dy + l[1]) + t[1];
-				pz[slot] = (float)(8 * dz + l[2]) + t[2];
-				if (ownslot >= 0) own[ownslot] = (uint16_t)slot;
+				py[slot] = (float)((int)d.x + l[1]) + t[1];
+				pz[slot] = (float)((int)d.y + l[2]) + t[2];
+				if (seg == 1 && d.w != ROW_NOT_OWN) own[d.w + slot] = (uint16_t)slot;  // the own list: slot order = fine-cell order
 			};
 			// CORR_STAGE_DEPTH records per thread in flight (a dense item stages ~3 600 = 7 per thread)
-			for (uint32_t slot0 = threadIdx.x; slot0 < total; slot0 += CORR_STAGE_DEPTH * T) {
+			const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+			for (uint32_t w0 = wave0; w0 < total; w0 += CORR_STAGE_DEPTH * T) {  // (uniform per wave: the ballots need every lane)
 				uint32_t src[CORR_STAGE_DEPTH];
-				int meta[CORR_STAGE_DEPTH], ownslot[CORR_STAGE_DEPTH];  // meta: seg | (dy + 1) << 2 | (dz + 1) << 4 | fy << 6 | fz << 10
+				int rs[CORR_STAGE_DEPTH];  // row | seg << 8
 				float4 rec[CORR_STAGE_DEPTH];
 #pragma unroll
 				for (int u = 0; u < CORR_STAGE_DEPTH; ++u) {
-					const uint32_t slot = slot0 + u * T;
-					src[u] = 0; meta[u] = 0; ownslot[u] = -1;
-					if (slot < total) {
-						int seg, dy, dz, fy, fz;
-						locate(slot, src[u], seg, dy, dz, fy, fz, ownslot[u]);
-						meta[u] = seg | ((dy + 1) << 2) | ((dz + 1) << 4) | (fy << 6) | (fz << 10);
+					const uint32_t wu = w0 + u * T, slot = wu + lane;
+					src[u] = 0; rs[u] = 0;
+					if (wu < total) {
+						const uint32_t last = wu + 63 < total ? wu + 63 : total - 1;
+						const int r_first = row_of(wu), r_last = row_of(last);
+						if (slot < total) locate(slot, r_first, r_last, src[u], rs[u]);
 					}
 				}
 #pragma unroll
 				for (int u = 0; u < CORR_STAGE_DEPTH; ++u) rec[u] = spos[src[u]];  // (src 0 for a slot beyond the end: any valid record)
 #pragma unroll
 				for (int u = 0; u < CORR_STAGE_DEPTH; ++u) {
-					const uint32_t slot = slot0 + u * T;
-					if (slot < total)
-						put(slot, rec[u], meta[u] & 3, ((meta[u] >> 2) & 3) - 1, ((meta[u] >> 4) & 3) - 1, (meta[u] >> 6) & 15, (meta[u] >> 10) & 15, ownslot[u]);
+					const uint32_t slot = w0 + u * T + lane;
+					if (slot < total) put(slot, rec[u], rs[u]);
 				}
 			}
 		}
@@ -780,7 +827,7 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			const float inv_re2 = (float)mp.inv_re2;
 			uint32_t j = 0xFFFFFFFFu;  // (the coincidence hash needs the particle's index: loaded by the rare branch only)
 			const uint32_t myrow = by + FB * bz;
-			const uint32_t grec = rowsrc[myrow * 3 + 1] + (me - (uint32_t)foff[myrow * FB + 1]);
+			const uint32_t grec = rowd[myrow * 8 + 1] + me;
 			auto pair2 = [&](uint32_t q, f2 qx, f2 qy, f2 qz) {
 				const f2 dx = mx - qx, dy = my - qy, dz = mz - qz;
 				const f2 d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
@@ -873,7 +920,8 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			float tme[3];
 			int lme[3];
 			const float4 rec = spos[grec];
-			fine_decode(rec, fy, fz, tme, lme);
+			const uint32_t yz = rowd[myrow * 8 + 6];
+			fine_decode_at(rec, (int)(yz & 255u), (int)(yz >> 8), tme, lme);
 			const uint32_t jj = __float_as_uint(rec.w);
 			const int c[3] = {8 * tx + lme[0], 8 * ty + lme[1], 8 * tz + lme[2]};
 			const double spring[3] = {(double)sx, (double)sy, (double)sz};
@@ -881,16 +929,20 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 #pragma unroll
 			for (int d = 0; d < 3; ++d) {
 				from[d] = (double)c[d] + (double)tme[d];
-				double x = from[d] + spring[d] * mp.corr;
-				to[d] = x < 0.0 ? 0.0 : ((double)nn[d] < x ? (double)nn[d] : x);
+				to[d] = from[d] + spring[d] * mp.corr;
 			}
 			// (a correction moves a particle by a fraction of a cell: in open water there is nothing to march against, only the
-			// domain walls push back)
-			if (mp.collide) {
-				if (!open_water || fabs(to[0] - from[0]) >= 7.0 || fabs(to[1] - from[1]) >= 7.0 || fabs(to[2] - from[2]) >= 7.0)
-					collide(g, solid, from, to, mp.skin);
-				else
-					collide_walls_only(g, to, mp.skin);
+			// domain walls push back - and a particle of an interior tile that moves less than 7 cells stays inside [1, n - 1):
+			// neither the clamp to the box nor the walls' push-out can fire)
+			if (!(lean && fabs(to[0] - from[0]) < 7.0 && fabs(to[1] - from[1]) < 7.0 && fabs(to[2] - from[2]) < 7.0)) {
+#pragma unroll
+				for (int d = 0; d < 3; ++d) to[d] = to[d] < 0.0 ? 0.0 : ((double)nn[d] < to[d] ? (double)nn[d] : to[d]);
+				if (mp.collide) {
+					if (!open_water || fabs(to[0] - from[0]) >= 7.0 || fabs(to[1] - from[1]) >= 7.0 || fabs(to[2] - from[2]) >= 7.0)
+						collide(g, solid, from, to, mp.skin);
+					else
+						collide_walls_only(g, to, mp.skin);
+				}
 			}
 			int nc[3];
 			float nt[3];

@@ -19,7 +19,7 @@ with tempfile.TemporaryDirectory() as d:
     asm = open(next(os.path.join(d, f) for f in os.listdir(d) if f.endswith("gfx950.s"))).read()
 for blk in asm.split("  - .agpr_count:")[1:]:
     get = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]  # noqa: E731
-    name = subprocess.run(["c++filt", get("name")], capture_output=True, text=True).stdout.strip()
+    name = subprocess.run(["c++filt", get("name")], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
     if flt in name:
         print(f"{name[5:name.index('(')] if name.startswith('void ') else name[:90]:60s} vgpr {get('vgpr_count'):>4} sgpr {get('sgpr_count'):>4} spill {get('vgpr_spill_count'):>3} "
               f"lds {get('group_segment_fixed_size'):>7} scratch {get('private_segment_fixed_size'):>5}")
