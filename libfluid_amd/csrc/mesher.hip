@@ -56,19 +56,20 @@ struct lfa_mesher {
 	size_t vcap = 0, icap = 0;
 	uint64_t n_vertices = 0, n_indices = 0;
 	bool have_mesh = false;
-	// vertex normals (lfa_mesher_normals): nothing of this exists until the first request
-	double *face = nullptr;        // per triangle: the cross product of its two edges
+	// vertex normals (lfa_mesher_normals, lfa_mesher_window_normals, lfa_mesher_download_boundary): nothing of this exists until
+	// the first request. Every handle then gets `face` and `vnorm`; vbelow only exists on a window with a layer below it
+	// (own_lo > 0, hence vsub > 0 possible), b_* only on a window with a layer above it (c_hi < n[2]). The whole grid has neither.
+	double *face = nullptr;        // per triangle: the cross product of its two edges (the first own layer's are the boundary)
 	double *vnorm = nullptr;       // per vertex
 	size_t fcap = 0, ncap = 0;
+	bool have_face = false;        // `face` holds the face vectors of the current mesh
 	bool have_normals = false;
 	uint64_t rebased = 0;          // what lfa_mesher_rebase has added to the indices of the current mesh
 	hipEvent_t nrm_ev[2] = {nullptr, nullptr};
 	float normals_ms = 0.0f;
-	// normals on a z-window (lfa_mesher_window_normals, lfa_mesher_download_boundary): nothing of this exists until the first request
 	uint32_t vsub = 0;             // vertices the cells of layer own_lo - 1 create (numbered here, stored by the window below)
 	double *vbelow = nullptr;      // their positions, recomputed from the planes own_lo - 1 .. own_lo: 3 vsub
 	size_t bvcap = 0;
-	bool have_face = false;        // `face` holds the face vectors of the current mesh (the first layer's are the boundary)
 	uint8_t *b_cases = nullptr;    // imported boundary: case bytes of layer c_hi (nx ny), their index offsets (nx ny + 1),
 	uint32_t *b_off = nullptr, *b_flag = nullptr;  // the first cell that contradicts the own layer below it
 	double *b_face = nullptr;      // and that layer's face vectors
@@ -89,6 +90,19 @@ int mfail(lfa_mesher *m, int code, const char *msg) {
 		if (e_ != hipSuccess) return mfail((m), e_ == hipErrorOutOfMemory ? LFA_E_OOM : LFA_E_HIP,  \
 		                                   (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
 	} while (0)
+
+/// (Re)allocates *p for `need` elements of `elem` bytes when the capacity is smaller; the contents are not kept. Every array of
+/// the handle that can outgrow its capacity is sized here, except the four particle arrays: they share one capacity and are
+/// released together before they are requested again (ensure_particle_capacity).
+template <typename T> int grow(lfa_mesher *m, T **p, size_t *cap, size_t need, size_t elem) {
+	if (need <= *cap) return LFA_OK;
+	if (*p) MSH_HIP(m, hipFree(*p));
+	*p = nullptr;
+	*cap = 0;
+	MSH_HIP(m, hipMalloc(p, need * elem));
+	*cap = need;
+	return LFA_OK;
+}
 
 // device copies of the case tables of mc_tables.h (filled at create time)
 __device__ uint8_t d_edge_corners[12 * 2];
@@ -427,6 +441,8 @@ k_mc_triangles(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const
 // the numbering above gives that order without a sort: the cells that share the vertex's grid edge lie at offsets
 // (dx, dy, dz) in {0, 1}^3 from the cell that owns it (edge_owner only steps to -1), ascending (dz, dy, dx) is ascending
 // cell index, triangles are numbered by cell (ibase) and inside a cell by the row of the case table.
+// There is one path: k_face_vectors, then k_vertex_normals, issued by normals() for lfa_mesher_normals (the whole grid) and
+// for lfa_mesher_window_normals (a z-window) alike; the face vectors are kept until the next extraction (have_face).
 // d_edge_in_neighbour[8 e + 4 dz + 2 dy + dx]: the number edge e of a cell has in the cell at that offset, MC_END where that
 // cell does not contain it (the inverse of edge_owner; filled at create time from the corner tables).
 __device__ uint8_t d_edge_in_neighbour[12 * 8];
@@ -452,80 +468,21 @@ void edge_in_neighbour_table(uint8_t out[12 * 8]) {
 		}
 }
 
-/// cross(p[i2] - p[i1], p[i3] - p[i1]) of every triangle (mesh.h:41-46, vec.h:546-548), one thread per triangle. `rebased`:
-/// what lfa_mesher_rebase has added to the index list since the extraction (the positions are stored from 0). An index that
-/// is not one of the nv vertices cannot come out of the extraction; it yields a NaN face vector rather than a read outside vpos.
-__global__ void __launch_bounds__(256)
-k_face_vectors(const double *vpos, const uint64_t *vidx, size_t nt, uint64_t rebased, uint64_t nv, double *face) {
-	const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= nt) return;
-	const uint64_t i1 = vidx[3 * t] - rebased, i2 = vidx[3 * t + 1] - rebased, i3 = vidx[3 * t + 2] - rebased;
-	if (i1 >= nv || i2 >= nv || i3 >= nv) {
-		face[3 * t] = face[3 * t + 1] = face[3 * t + 2] = __builtin_nan("");
-		return;
-	}
-	const double *p1 = vpos + 3 * i1, *p2 = vpos + 3 * i2, *p3 = vpos + 3 * i3;
-	const double ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
-	const double bx = p3[0] - p1[0], by = p3[1] - p1[1], bz = p3[2] - p1[2];
-	face[3 * t] = ay * bz - az * by;
-	face[3 * t + 1] = az * bx - ax * bz;
-	face[3 * t + 2] = ax * by - ay * bx;
-}
-
-/// The normal of every vertex a cell creates: its triangles' face vectors gathered in ascending triangle index (mesh.h:47-49),
-/// then normalized_checked or (1, 0, 0) (mesh.h:50-52, vec.h:377-399). One thread per cell; whole grid only (no z-window).
-__global__ void __launch_bounds__(256)
-k_vertex_normals(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const uint32_t *vbase, const uint32_t *ibase,
-                 const double *face, double *vnorm) {
-	const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= g.nx * g.ny * g.nzl) return;
-	const uint32_t mine = created[c];
-	if (!mine) return;
-	const uint64_t x = c % g.nx, y = (c / g.nx) % g.ny, z = c / (g.nx * g.ny);
-	const uint32_t vb = vbase[c];
-	for (int e = 0; e < 12; ++e) {
-		if (!(mine & (1u << e))) continue;
-		double sx = 0.0, sy = 0.0, sz = 0.0;
-		for (int j = 0; j < 8; ++j) {
-			const uint8_t ne = d_edge_in_neighbour[8 * e + j];
-			const uint64_t dx = j & 1, dy = (j >> 1) & 1, dz = j >> 2;
-			if (ne == MC_END || x + dx >= g.nx || y + dy >= g.ny || z + dz >= g.nzl) continue;
-			const size_t nc = c + dx + g.nx * (dy + g.ny * dz);
-			const uint8_t *row = d_tri_table + 16 * (size_t)occ_in[nc];
-			if (row[0] == MC_END) continue;
-			const double *f = face + ibase[nc];  // 3 doubles per triangle = 1 per index
-			for (int k = 0; k < 15 && row[k] != MC_END; k += 3) {
-				if (row[k] != ne && row[k + 1] != ne && row[k + 2] != ne) continue;
-				sx += f[k];
-				sy += f[k + 1];
-				sz += f[k + 2];
-			}
-		}
-		double sq = 0.0;  // vec_ops::dot
-		sq += sx * sx;
-		sq += sy * sy;
-		sq += sz * sz;
-		double *o = vnorm + 3 * ((size_t)vb + __popc(mine & before_mask(e)));
-		if (sq <= 1e-6 * 1e-6) {
-			o[0] = 1.0; o[1] = 0.0; o[2] = 0.0;
-		} else {  // (a NaN sum comes here too and stays NaN)
-			const double len = sqrt(sq);
-			o[0] = sx / len; o[1] = sy / len; o[2] = sz / len;
-		}
-	}
-}
-
-// ---- the same on a z-window (lfa_mesher_window_normals). Two things differ from the whole grid. The triangles of the first own
+// A z-window (the whole grid is the window [0, nz) and takes the same path) adds two things. The triangles of the first own
 // layer refer to vertices of the plane own_lo, which the window below stores: k_mc_vertices_below recomputes them. And the
 // vertices on the plane c_hi have triangles in layer c_hi, the first layer of the window above; they come last in such a
 // vertex's ordered sum (z is the slowest axis of the triangle numbering), so the sum is simply continued with that layer's face
 // vectors, which the window above exports (its "boundary": case bytes and face vectors of its layer own_lo, a prefix of its
 // triangle list).
 
-/// k_face_vectors on a window: a relative index in [-vsub, 0) is a vertex of the layer below and reads vbelow.
+/// cross(p[i2] - p[i1], p[i3] - p[i1]) of every triangle (mesh.h:41-46, vec.h:546-548), one thread per triangle. `rebased`:
+/// what lfa_mesher_rebase has added to the index list since the extraction (the positions are stored from 0). A relative index
+/// in [-vsub, 0) is a vertex of the layer below and reads vbelow. Any other index that is not one of the nv vertices cannot come
+/// out of the extraction; it yields a NaN face vector rather than a read outside vpos. The whole grid has vsub = 0 and a null
+/// vbelow: `b < vsub` is then false for every b, so vbelow is not dereferenced.
 __global__ void __launch_bounds__(256)
-k_window_face_vectors(const double *vpos, const double *vbelow, const uint64_t *vidx, size_t nt, uint64_t rebased, uint64_t nv,
-                      uint64_t vsub, double *face) {
+k_face_vectors(const double *vpos, const double *vbelow, const uint64_t *vidx, size_t nt, uint64_t rebased, uint64_t nv,
+               uint64_t vsub, double *face) {
 	const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= nt) return;
 	const double *p[3];
@@ -560,13 +517,15 @@ k_boundary_setup(MeshGrid g, const uint8_t *occ_in, const uint8_t *b_cases, uint
 	if ((above & 0xF) != (own >> 4)) atomicMin(flag, (uint32_t)k);
 }
 
-/// k_vertex_normals on a window: one thread per cell of the own layers [own_lo, c_hi) (the cells of layer own_lo - 1 are
-/// numbered here but belong to the window below); vertex slots are vbase - vsub. A neighbour in layer c_hi < nz is read from the
-/// imported boundary (locally that layer is classified as empty). Without a layer above (c_hi == nz) b_* are not read.
+/// The normal of every vertex a cell creates: its triangles' face vectors gathered in ascending triangle index (mesh.h:47-49),
+/// then normalized_checked or (1, 0, 0) (mesh.h:50-52, vec.h:377-399). One thread per cell of the own layers [own_lo, c_hi) (the
+/// cells of layer own_lo - 1 are numbered here but belong to the window below); vertex slots are vbase - vsub. A neighbour in
+/// layer c_hi < nz is read from the imported boundary (locally that layer is classified as empty). Without a layer above
+/// (c_hi == nz, the whole grid among them) b_* are null and not dereferenced: z + dz == c_hi does not pass the `>= g.nz` test.
 __global__ void __launch_bounds__(256)
-k_window_vertex_normals(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const uint32_t *vbase, const uint32_t *ibase,
-                        const double *face, uint32_t vsub, const uint8_t *b_cases, const uint32_t *b_off, const double *b_face,
-                        double *vnorm) {
+k_vertex_normals(MeshGrid g, const uint8_t *occ_in, const uint16_t *created, const uint32_t *vbase, const uint32_t *ibase,
+                 const double *face, uint32_t vsub, const uint8_t *b_cases, const uint32_t *b_off, const double *b_face,
+                 double *vnorm) {
 	const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= g.nx * g.ny * g.nzl) return;
 	const uint32_t mine = created[c];
@@ -725,19 +684,15 @@ static int sample_device_positions(lfa_mesher *m, const double *dpos, uint64_t n
 	MSH_HIP(m, hipMemsetAsync(m->cell_start, 0, (m->ncell + 1) * 4, m->stream));
 	MSH_HIP(m, hipMemsetAsync(m->cell_fill, 0, m->ncell * 4, m->stream));
 	const size_t nbf = (size_t)((m->n[0] + 7) >> 3) * ((m->n[1] + 7) >> 3) * ((m->nzl + 7) >> 3);
-	if (nbf > m->n_blk_flag) {
-		if (m->blk_flag) MSH_HIP(m, hipFree(m->blk_flag));
-		m->blk_flag = nullptr;
-		MSH_HIP(m, hipMalloc(&m->blk_flag, nbf));
-		m->n_blk_flag = nbf;
-	}
+	int rc = grow(m, &m->blk_flag, &m->n_blk_flag, nbf, 1);
+	if (rc != LFA_OK) return rc;
 	MSH_HIP(m, hipMemsetAsync(m->blk_flag, 0, nbf, m->stream));
 	if (n) {
 		hipLaunchKernelGGL(k_count_particles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, g, dpos, (size_t)n,
 		                   m->cell_start, m->blk_flag);
 		MSH_HIP(m, hipGetLastError());
 	}
-	int rc = scan_u32(m, m->cell_start, m->cell_start, m->ncell);
+	rc = scan_u32(m, m->cell_start, m->cell_start, m->ncell);
 	if (rc != LFA_OK) return rc;
 	if (n) {
 		hipLaunchKernelGGL(k_scatter_particles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, g, dpos, (size_t)n,
@@ -889,20 +844,9 @@ extern "C" int lfa_mesher_marching_cubes(lfa_mesher *m, uint64_t *n_vertices, ui
 	MSH_HIP(m, hipStreamSynchronize(m->stream));
 	const uint32_t vsub = tot[2], nv = tot[0] - tot[2];
 	m->vsub = vsub;
-	if (nv > m->vcap) {
-		if (m->vpos) MSH_HIP(m, hipFree(m->vpos));
-		m->vpos = nullptr;
-		m->vcap = 0;
-		MSH_HIP(m, hipMalloc(&m->vpos, (size_t)nv * 24));
-		m->vcap = nv;
-	}
-	if (tot[1] > m->icap) {
-		if (m->vidx) MSH_HIP(m, hipFree(m->vidx));
-		m->vidx = nullptr;
-		m->icap = 0;
-		MSH_HIP(m, hipMalloc(&m->vidx, (size_t)tot[1] * 8));
-		m->icap = tot[1];
-	}
+	rc = grow(m, &m->vpos, &m->vcap, (size_t)nv, 24);
+	if (rc == LFA_OK) rc = grow(m, &m->vidx, &m->icap, (size_t)tot[1], 8);
+	if (rc != LFA_OK) return rc;
 	if (tot[0]) {
 		hipLaunchKernelGGL(k_mc_vertices, dim3(grid), dim3(256), 0, m->stream, g, (const double *)m->values,
 		                   (const uint16_t *)m->created, (const uint32_t *)m->vcount, m->vpos, vsub);
@@ -945,47 +889,6 @@ extern "C" int lfa_mesher_download_mesh(lfa_mesher *m, double *positions, uint64
 	return LFA_OK;
 }
 
-extern "C" int lfa_mesher_normals(lfa_mesher *m) {
-	if (!m) return LFA_E_INVALID;
-	if (m->own_lo != 0 || m->c_hi != m->n[2])
-		return mfail(m, LFA_E_UNSUPPORTED, "lfa_mesher_normals: a z-window does not hold every triangle of the vertices on its upper plane; "
-		                                    "normals need the whole grid on one handle");
-	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, "lfa_mesher_normals: no current mesh, call lfa_mesher_marching_cubes first");
-	MSH_HIP(m, hipSetDevice(m->device));
-	const size_t nv = (size_t)m->n_vertices, nt = (size_t)(m->n_indices / 3);
-	m->normals_ms = 0.0f;
-	if (nv && nt) {
-		if (nv > m->ncap) {
-			if (m->vnorm) MSH_HIP(m, hipFree(m->vnorm));
-			m->vnorm = nullptr;
-			m->ncap = 0;
-			MSH_HIP(m, hipMalloc(&m->vnorm, nv * 24));
-			m->ncap = nv;
-		}
-		if (nt > m->fcap) {
-			if (m->face) MSH_HIP(m, hipFree(m->face));
-			m->face = nullptr;
-			m->fcap = 0;
-			MSH_HIP(m, hipMalloc(&m->face, nt * 24));
-			m->fcap = nt;
-		}
-		for (hipEvent_t &e : m->nrm_ev)
-			if (!e) MSH_HIP(m, hipEventCreate(&e));
-		MSH_HIP(m, hipEventRecord(m->nrm_ev[0], m->stream));
-		hipLaunchKernelGGL(k_face_vectors, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, m->stream, (const double *)m->vpos,
-		                   (const uint64_t *)m->vidx, nt, m->rebased, (uint64_t)nv, m->face);
-		hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((m->ncell + 255) / 256)), dim3(256), 0, m->stream, make_grid(m),
-		                   (const uint8_t *)m->occ, (const uint16_t *)m->created, (const uint32_t *)m->vcount,
-		                   (const uint32_t *)m->icount, (const double *)m->face, m->vnorm);
-		MSH_HIP(m, hipGetLastError());
-		MSH_HIP(m, hipEventRecord(m->nrm_ev[1], m->stream));
-		MSH_HIP(m, hipStreamSynchronize(m->stream));
-		MSH_HIP(m, hipEventElapsedTime(&m->normals_ms, m->nrm_ev[0], m->nrm_ev[1]));
-	}
-	m->have_normals = true;
-	return LFA_OK;
-}
-
 extern "C" int lfa_mesher_normals_time(lfa_mesher *m, double *ms) {
 	if (!m || !ms) return LFA_E_INVALID;
 	if (!m->have_mesh || !m->have_normals)
@@ -1006,18 +909,6 @@ extern "C" int lfa_mesher_download_normals(lfa_mesher *m, double *normals) {
 	return LFA_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ normals on a z-window
-/// (Re)allocates *p for `need` elements of `elem` bytes when the capacity is smaller.
-template <typename T> static int grow(lfa_mesher *m, T **p, size_t *cap, size_t need, size_t elem) {
-	if (need <= *cap) return LFA_OK;
-	if (*p) MSH_HIP(m, hipFree(*p));
-	*p = nullptr;
-	*cap = 0;
-	MSH_HIP(m, hipMalloc(p, need * elem));
-	*cap = need;
-	return LFA_OK;
-}
-
 /// The face vectors of the current mesh into m->face (launched on the stream, not waited for), unless they are there already.
 static int ensure_face(lfa_mesher *m) {
 	const size_t nt = (size_t)(m->n_indices / 3);
@@ -1028,7 +919,7 @@ static int ensure_face(lfa_mesher *m) {
 	if (m->vsub)
 		hipLaunchKernelGGL(k_mc_vertices_below, dim3((unsigned)((m->n[0] * m->n[1] + 255) / 256)), dim3(256), 0, m->stream, make_grid(m),
 		                   (const double *)m->values, (const uint16_t *)m->created, (const uint32_t *)m->vcount, m->vbelow);
-	hipLaunchKernelGGL(k_window_face_vectors, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, m->stream, (const double *)m->vpos,
+	hipLaunchKernelGGL(k_face_vectors, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, m->stream, (const double *)m->vpos,
 	                   (const double *)m->vbelow, (const uint64_t *)m->vidx, nt, m->rebased, m->n_vertices, (uint64_t)m->vsub, m->face);
 	MSH_HIP(m, hipGetLastError());
 	m->have_face = true;
@@ -1073,18 +964,20 @@ extern "C" int lfa_mesher_download_boundary(lfa_mesher *m, uint8_t *cases, doubl
 	return LFA_OK;
 }
 
-/// cases_above / face_above: host memory or memory of m's device (lfa_mesher_window_normals_from).
-static int window_normals(lfa_mesher *m, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above) {
+/// The one normals pass behind both entry points; `who` names the caller in the error messages. cases_above / face_above: the
+/// boundary of the window above, in host memory or memory of m's device (lfa_mesher_window_normals_from); none for a window that
+/// reaches the top of the grid, the whole grid among them.
+static int normals(lfa_mesher *m, const std::string &who, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above) {
 	if (!m) return LFA_E_INVALID;
 	m->have_normals = false;  // until this call has succeeded
-	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: no current mesh, call lfa_mesher_marching_cubes first");
+	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, (who + ": no current mesh, call lfa_mesher_marching_cubes first").c_str());
 	const bool top = m->c_hi == m->n[2];
 	if (top && (cases_above || face_above || n_triangles_above))
-		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: the window reaches the top of the grid, there is no boundary above it");
+		return mfail(m, LFA_E_INVALID, (who + ": the window reaches the top of the grid, there is no boundary above it").c_str());
 	if (!top && (!cases_above || (!face_above && n_triangles_above)))
-		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: a window below the top of the grid needs the boundary of the window above");
+		return mfail(m, LFA_E_INVALID, (who + ": a window below the top of the grid needs the boundary of the window above").c_str());
 	if (n_triangles_above > 5 * m->n[0] * m->n[1])
-		return mfail(m, LFA_E_INVALID, "lfa_mesher_window_normals: n_triangles_above is more than a layer of cells can hold");
+		return mfail(m, LFA_E_INVALID, (who + ": n_triangles_above is more than a layer of cells can hold").c_str());
 	MSH_HIP(m, hipSetDevice(m->device));
 	const size_t nv = (size_t)m->n_vertices, nt = (size_t)(m->n_indices / 3), nxy = (size_t)(m->n[0] * m->n[1]);
 	const MeshGrid g = make_grid(m);
@@ -1120,21 +1013,21 @@ static int window_normals(lfa_mesher *m, const uint8_t *cases_above, const doubl
 		MSH_HIP(m, hipEventElapsedTime(&ms[0], m->nrm_ev[0], m->nrm_ev[1]));
 		if ((uint64_t)total != 3 * n_triangles_above) {
 			char msg[200];
-			snprintf(msg, sizeof msg, "lfa_mesher_window_normals: cases_above hold %llu triangles, n_triangles_above is %llu",
+			snprintf(msg, sizeof msg, "%s: cases_above hold %llu triangles, n_triangles_above is %llu", who.c_str(),
 			         (unsigned long long)(total / 3), (unsigned long long)n_triangles_above);
 			return mfail(m, LFA_E_INVALID, msg);
 		}
 		if (bad != 0xFFFFFFFFu) {
 			char msg[240];
-			snprintf(msg, sizeof msg, "lfa_mesher_window_normals: the boundary does not fit this window's mesh (stale, or of another window): "
-			         "first at cell (%llu, %llu) of layer %llu", (unsigned long long)(bad % m->n[0]), (unsigned long long)(bad / m->n[0]),
-			         (unsigned long long)m->c_hi);
+			snprintf(msg, sizeof msg, "%s: the boundary does not fit this window's mesh (stale, or of another window): "
+			         "first at cell (%llu, %llu) of layer %llu", who.c_str(), (unsigned long long)(bad % m->n[0]),
+			         (unsigned long long)(bad / m->n[0]), (unsigned long long)m->c_hi);
 			return mfail(m, LFA_E_INVALID, msg);
 		}
 		MSH_HIP(m, hipEventRecord(m->nrm_ev[0], m->stream));
 	}
 	if (nv && nt) {
-		hipLaunchKernelGGL(k_window_vertex_normals, dim3((unsigned)((m->ncell + 255) / 256)), dim3(256), 0, m->stream, g,
+		hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((m->ncell + 255) / 256)), dim3(256), 0, m->stream, g,
 		                   (const uint8_t *)m->occ, (const uint16_t *)m->created, (const uint32_t *)m->vcount, (const uint32_t *)m->icount,
 		                   (const double *)m->face, m->vsub, (const uint8_t *)m->b_cases, (const uint32_t *)m->b_off,
 		                   (const double *)m->b_face, m->vnorm);
@@ -1149,7 +1042,17 @@ static int window_normals(lfa_mesher *m, const uint8_t *cases_above, const doubl
 }
 
 extern "C" int lfa_mesher_window_normals(lfa_mesher *m, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above) {
-	return window_normals(m, cases_above, face_above, n_triangles_above);
+	return normals(m, "lfa_mesher_window_normals", cases_above, face_above, n_triangles_above);
+}
+
+/// The whole grid is the window [0, n[2]) without a layer below or above. Refused on any other window before the handle's state
+/// is touched: the window normals it may hold stay valid.
+extern "C" int lfa_mesher_normals(lfa_mesher *m) {
+	if (!m) return LFA_E_INVALID;
+	if (m->own_lo != 0 || m->c_hi != m->n[2])
+		return mfail(m, LFA_E_UNSUPPORTED, "lfa_mesher_normals: a z-window does not hold every triangle of the vertices on its upper plane; "
+		                                    "normals need the whole grid on one handle");
+	return normals(m, "lfa_mesher_normals", nullptr, nullptr, 0);
 }
 
 extern "C" int lfa_mesher_window_normals_from(lfa_mesher *m, lfa_mesher *above) {
@@ -1170,10 +1073,10 @@ extern "C" int lfa_mesher_window_normals_from(lfa_mesher *m, lfa_mesher *above) 
 		std::vector<double> face(3 * (size_t)nt + 1);
 		rc = lfa_mesher_download_boundary(above, cases.data(), face.data());
 		if (rc != LFA_OK) return mfail(m, rc, above->err.c_str());
-		return window_normals(m, cases.data(), face.data(), nt);
+		return normals(m, "lfa_mesher_window_normals", cases.data(), face.data(), nt);
 	}
 	rc = ensure_face(above);
 	if (rc != LFA_OK) return mfail(m, rc, above->err.c_str());
 	MSH_HIP(m, hipStreamSynchronize(above->stream));  // its face vectors are read from m's stream below
-	return window_normals(m, above->occ + nxy * (size_t)(above->own_lo - above->z0), nt ? above->face : nullptr, nt);
+	return normals(m, "lfa_mesher_window_normals", above->occ + nxy * (size_t)(above->own_lo - above->z0), nt ? above->face : nullptr, nt);
 }

@@ -400,6 +400,41 @@ def test_a_window_that_never_asks_allocates_nothing_more(golden):
 
 
 @pytest.mark.gpu
+def test_the_two_entry_points_share_one_path_and_one_state(golden):
+    """lfa_mesher_normals is the window path without a boundary: on a whole-grid handle either entry point gives the reference's
+    rows from the same two buffers, whatever lfa_mesher_rebase did in between (the cached face vectors are those of the unshifted
+    mesh); on a window the refusal comes before the state is touched; every refusal names the entry point that was called."""
+    name = "field1"
+    kw, v = field_case(name, golden)
+    want = golden[f"{name}_normals"]
+
+    def requests():
+        s = lfa.pool_stats()
+        return s["hits"] + s["misses"]
+
+    m = lfa.Mesher(**kw)
+    msg = refused(m.compute_normals, E_INVALID, "lfa_mesher_normals")  # before any extraction
+    assert "lfa_mesher_window_normals" not in msg
+    m.set_values(v)
+    m.marching_cubes()
+    assert same(m.normals(), want) and m.normals_ms() > 0.0
+    n1 = requests()
+    m.rebase(5)
+    assert same(m.window_normals(), want) and m.normals_ms() > 0.0
+    assert same(m.normals(), want) and m.normals_ms() > 0.0
+    assert requests() == n1              # both entry points use the same two buffers
+    m.close()
+
+    ms, _ = field_windows(name, [0, 2, 3, kw["size"][2]], golden)
+    lo, mid, top = ms
+    rows = lo.window_normals(mid)
+    assert same(rows, want[:lo._counts[0]])
+    refused(lo.compute_normals, E_UNSUPPORTED, "window")
+    assert same(lo.download_normals(), rows)  # the refusal spoils nothing
+    close_all(ms)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("bounds", [[0, 2, 4], [0, 1, 2, 3, 4]])
 def test_slab_ranks_stitch_their_normals(bounds):
     """The run of tests/test_gpu_slabs.py::test_slab_ranks_mesh_their_windows_into_the_single_domain_mesh with normals. The

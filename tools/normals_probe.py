@@ -7,7 +7,8 @@ same mesh. Not bench.py: a measurement of one call, on two meshes -
 
 For each: medians over --reps repetitions after --warmup warm-ups of
   device  HIP-event time of lfa_mesher_normals alone on the mesher's stream (lfa_mesher_normals_time), and the wall time of
-          compute + download of the normals;
+          compute + download of the normals; every repetition starts from a fresh extraction, so the face vectors are
+          computed inside it;
   host    wall time of the loop on the downloaded mesh (tools/normals_host_loop.cpp, g++ -O2, one thread);
 and the bytes the device pass must move at the least (24 nv written + 8 ni indices + 24 nv positions read once), hence its share
 of the measured 5.8-6.2 TB/s copy ceiling. The two results are also compared (NaN beside NaN counts as equal).
@@ -129,6 +130,7 @@ def child(name, reps, warmup, windows=()):
               file=sys.stderr, flush=True)
     ev, compute, total = [], [], []
     for k in range(warmup + reps):
+        m.marching_cubes()  # (a fresh mesh: no cached face vectors, every repetition holds both passes)
         t0 = time.perf_counter()
         m.compute_normals()  # (returns after the stream has drained)
         t1 = time.perf_counter()
