@@ -11,8 +11,9 @@
 //   surface  : one wave per triangle, lanes stride over the cells of the triangle's bounding box; marking is an
 //              idempotent byte store, so overlapping triangles need no atomics.
 //   exterior : the reference's stack flood fill from voxel (0,0,0) (src/voxelizer.cpp:83-124) computes the 6-connected
-//              component of non-surface cells that contains the corner; here 8^3 blocks relax to their local fixed point
-//              in LDS and the launch is repeated until no block changes -- the same set, any order.
+//              component of interior cells that contains the corner (a cell that is already exterior is a wall, so the
+//              result is the reference's on a grid a host has edited too); here 8^3 blocks relax to their local fixed
+//              point in LDS and the launch is repeated until no block changes -- the same set, any order.
 //   lists    : ordered stream compaction in raw (x fastest) order = grid3::for_each / for_each_in_range order.
 #include "common.h"
 
@@ -236,6 +237,16 @@ k_flood_pass(uint8_t *vox, uint64_t nx, uint64_t ny, uint64_t nz, int *changed) 
 
 __global__ void k_seed_corner(uint8_t *vox) {
 	if (vox[0] != LFA_VOX_SURFACE) vox[0] = LFA_VOX_EXTERIOR;  // src/voxelizer.cpp:88-91
+}
+
+/// Cells that are exterior when mark_exterior is entered are never pushed by the reference (check_push takes interior cells
+/// only, src/voxelizer.cpp:94-100): they are walls of the fill. For the duration of the passes they carry VOX_STALE, which
+/// k_flood_pass neither spreads from nor changes; no other entry point ever sees it.
+constexpr uint8_t VOX_STALE = 3;
+__global__ void __launch_bounds__(256)
+k_rename(uint8_t *vox, size_t nc, uint8_t from, uint8_t to) {
+	for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < nc; r += (size_t)gridDim.x * 256)
+		if (vox[r] == from) vox[r] = to;
 }
 
 struct Select {
@@ -463,11 +474,8 @@ extern "C" int lfa_voxels_voxelize_triangles(lfa_voxels *v, const double *positi
 	return rc;
 }
 
-extern "C" int lfa_voxels_mark_exterior(lfa_voxels *v) {
-	if (!v) return LFA_E_INVALID;
-	if (v->nc == 0) return LFA_OK;  // src/voxelizer.cpp:84-86
-	VOX_HIP(v, hipSetDevice(v->device));
-	hipLaunchKernelGGL(k_seed_corner, dim3(1), dim3(1), 0, v->stream, v->vox);
+/// The relaxation passes of lfa_voxels_mark_exterior, from the seeded corner to the fixed point.
+static int flood_to_fixed_point(lfa_voxels *v) {
 	const dim3 grid((unsigned)((v->n[0] + 7) / 8), (unsigned)((v->n[1] + 7) / 8), (unsigned)((v->n[2] + 7) / 8));
 	const int batch = 8;
 	for (int guard = 0; guard < (1 << 20); ++guard) {
@@ -481,6 +489,25 @@ extern "C" int lfa_voxels_mark_exterior(lfa_voxels *v) {
 		if (!changed) return LFA_OK;
 	}
 	return vfail(v, LFA_E_HIP, "lfa_voxels_mark_exterior: flood fill did not reach a fixed point");
+}
+
+extern "C" int lfa_voxels_mark_exterior(lfa_voxels *v) {
+	if (!v) return LFA_E_INVALID;
+	if (v->nc == 0) return LFA_OK;  // src/voxelizer.cpp:84-86
+	VOX_HIP(v, hipSetDevice(v->device));
+	uint8_t corner = LFA_VOX_INTERIOR;
+	VOX_HIP(v, hipMemcpyAsync(&corner, v->vox, 1, hipMemcpyDeviceToHost, v->stream));
+	VOX_HIP(v, hipStreamSynchronize(v->stream));
+	if (corner == LFA_VOX_SURFACE) return LFA_OK;  // src/voxelizer.cpp:87-89
+	const unsigned rb = (unsigned)std::min<size_t>((v->nc + 255) / 256, 4096);
+	hipLaunchKernelGGL(k_rename, dim3(rb), dim3(256), 0, v->stream, v->vox, v->nc, (uint8_t)LFA_VOX_EXTERIOR, VOX_STALE);
+	hipLaunchKernelGGL(k_seed_corner, dim3(1), dim3(1), 0, v->stream, v->vox);
+	int rc = flood_to_fixed_point(v);
+	// whatever the passes met, the private value leaves the grid again
+	hipLaunchKernelGGL(k_rename, dim3(rb), dim3(256), 0, v->stream, v->vox, v->nc, VOX_STALE, (uint8_t)LFA_VOX_EXTERIOR);
+	if ((hipGetLastError() != hipSuccess || hipStreamSynchronize(v->stream) != hipSuccess) && rc == LFA_OK)
+		rc = vfail(v, LFA_E_HIP, "lfa_voxels_mark_exterior: kernel failed");
+	return rc;
 }
 
 static int select_cells(lfa_voxels *v, int interior, int surface, const int64_t *ref, uint64_t *count, bool write) {

@@ -321,6 +321,34 @@ def voxelize(positions, indices, cell_size=1.0, ref_grid_offset=(0.0, 0.0, 0.0),
     return gmin, goff, types.reshape(int(size[2]), int(size[1]), int(size[0]))
 
 
+def voxel_triangles(types, grid_offset, cell_size, positions, indices, kind="oracle"):
+    """voxelize_mesh_surface on a grid the caller supplies (types uint8[nz, ny, nx], public members voxels / grid_offset /
+    cell_size). The triangles must lie inside the grid, as the reference requires. Returns a new array."""
+    L = _get(kind).lib
+    out = np.array(types, dtype=np.uint8, order="C", copy=True)
+    n = np.array(out.shape[::-1], dtype=np.uint64)
+    pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    assert idx.size == 0 or int(idx.max()) < pos.shape[0]
+    off = np.asarray(grid_offset, dtype=np.float64)
+    fn = getattr(L, ("orc_" if kind == "oracle" else "ref_") + "vox_triangles")
+    fn.restype, fn.argtypes = None, [_vp, _vp, _vp, _dbl, _vp, _sz, _vp, _sz]
+    fn(_ptr(out), _ptr(n), _ptr(off), float(cell_size), _ptr(pos), pos.shape[0], _ptr(idx), idx.size)
+    return out
+
+
+def voxel_mark_exterior(types, kind="oracle"):
+    """mark_exterior on a grid the caller supplies (types uint8[nz, ny, nx] of the three cell types). Returns a new array."""
+    L = _get(kind).lib
+    out = np.array(types, dtype=np.uint8, order="C", copy=True)
+    assert out.ndim == 3
+    n = np.array(out.shape[::-1], dtype=np.uint64)
+    fn = getattr(L, ("orc_" if kind == "oracle" else "ref_") + "vox_mark_exterior")
+    fn.restype, fn.argtypes = None, [_vp, _vp]
+    fn(_ptr(out), _ptr(n))
+    return out
+
+
 def ref_voxel_cells(positions, indices, cell_size, ref_grid_offset, include_interior, include_surface, ref_grid_size=None):
     """Cell lists of the Maya VoxelizerNode computed with the real reference's voxelizer and grid3::for_each
     (plugins/maya/nodes/voxelizer_node.cpp:285-343) as int32[k,3]; ref_grid_size=None: voxel-grid coordinates."""

@@ -392,6 +392,37 @@ extern "C" {
 	}
 }
 
+// ---- voxelizer stages on a caller's grid: a host sets the public members and calls one stage (include/fluid/voxelizer.h:55-70)
+namespace {
+	void set_voxels(fluid::voxelizer &vox, const std::uint8_t *types, const std::uint64_t *n) {
+		vox.voxels = fluid::grid3<fluid::voxelizer::cell_type>(vec3s(n[0], n[1], n[2]), fluid::voxelizer::cell_type::interior);
+		for (std::size_t i = 0; i < n[0] * n[1] * n[2]; ++i) vox.voxels[i] = static_cast<fluid::voxelizer::cell_type>(types[i]);
+	}
+	void get_voxels(const fluid::voxelizer &vox, std::uint8_t *types, const std::uint64_t *n) {
+		for (std::size_t i = 0; i < n[0] * n[1] * n[2]; ++i) types[i] = static_cast<std::uint8_t>(vox.voxels[i]);
+	}
+}
+extern "C" {
+	void ref_vox_triangles(
+		std::uint8_t *types, const std::uint64_t *n, const double *off, double cs, const double *pos, std::size_t nv,
+		const std::uint64_t *idx, std::size_t ni
+	) {
+		auto m = make_mesh(pos, nv, idx, ni);
+		fluid::voxelizer vox;
+		set_voxels(vox, types, n);
+		vox.grid_offset = vec3d(off[0], off[1], off[2]);
+		vox.cell_size = cs;
+		vox.voxelize_mesh_surface(m);
+		get_voxels(vox, types, n);
+	}
+	void ref_vox_mark_exterior(std::uint8_t *types, const std::uint64_t *n) {
+		fluid::voxelizer vox;
+		set_voxels(vox, types, n);
+		vox.mark_exterior();
+		get_voxels(vox, types, n);
+	}
+}
+
 // ---- formats (include/fluid/data_structures/point_cloud.h, mesh.h) ----------------------------------------------------
 namespace {
 	std::size_t emit(const std::string &s, char *buf, std::size_t cap) {

@@ -149,3 +149,19 @@ void orc_voxelize(const double *pos, size_t nv, const uint64_t *idx, size_t ni, 
 	}
 	mark_exterior(types, n);
 }
+
+/* The two stages on a caller's grid, the way a host of the reference uses the public members `voxels`, `grid_offset` and
+ * `cell_size` (include/fluid/voxelizer.h:55-70): voxelize_mesh_surface, then mark_exterior, each on whatever the grid holds. */
+void orc_vox_triangles(uint8_t *types, const uint64_t *n, const double *off, double cs, const double *pos, size_t nv,
+                       const uint64_t *idx, size_t ni) {
+	(void)nv;
+	for (size_t i = 0; i + 2 < ni; i += 3) {
+		v3 p[3];
+		for (int k = 0; k < 3; ++k) {
+			p[k].x = pos[3 * idx[i + k]]; p[k].y = pos[3 * idx[i + k] + 1]; p[k].z = pos[3 * idx[i + k] + 2];
+		}
+		voxelize_triangle(types, n, off, cs, p[0], p[1], p[2]);
+	}
+}
+
+void orc_vox_mark_exterior(uint8_t *types, const uint64_t *n) { mark_exterior(types, n); }
