@@ -162,6 +162,34 @@ int lfa_frame_stats_time(lfa_sim *s, double *ms);
  * device to host, nothing host to device. LFA_E_INVALID, nothing written: n is not the resident count, cell_size unset, an
  * unbinned slab handle. */
 int lfa_download_positions(lfa_sim *s, double *xyz, uint64_t n);
+/* -- grid velocity at points of the caller's choosing -------------------------------------------------------------------------
+ * lfa_sample_velocity(s, x) is the velocity the reference's PIC grid-to-particle transfer gives a particle at world position x, on
+ * the grid that lfa_download_cells(s) would return at that moment, computed in fp64 with the reference's operations in the
+ * reference's order, so it equals the oracle on that download bit for bit (simulation::_transfer_from_grid_pic,
+ * src/simulation.cpp:447-461, through mac_grid::get_face_samples, src/mac_grid.cpp:42-112, and trilerp,
+ * include/fluid/misc.h:20-36). What it replaces: the download of every cell (32 bytes each) and the host's own copy of those
+ * loops - the testbed's grid_vels (testbed/main.cpp:70-78), velocities for motion blur, foam and tracer points.
+ *   cell, fraction : fi = (x - grid_offset) / cell_size per axis, a true fp64 division; cell = trunc(fi), t = fi - cell, fp64
+ *                    (particle::compute_cell_index_and_position, src/simulation.cpp:17-23).
+ *   inside         : fi >= 0 && fi < n on all three axes, decided before any cast: false for NaN, +-inf and huge values. The
+ *                    reference never asks about other points (its advection clamps them first); here they get velocity
+ *                    (+0.0, +0.0, +0.0) and type 0, and *n_outside counts them.
+ *   samples        : the 3 x 3 x 3 block around the cell under _clamp's rule (src/mac_grid.cpp:42-50): an index below 0 or at or
+ *                    above n - 1 - the last cell counts as clamped - replicates the border cell and zeroes the component along
+ *                    that axis; tmid = t - 0.5, shifted by one cell when negative; the three trilerps with the argument order of
+ *                    src/simulation.cpp:451-459 and lerp(a, b, t) = a (1 - t) + b t.
+ *   xyz            : double[3 n] world positions (host memory), staged through the handle's io buffer; n < 2^32.
+ *   velocity       : double[3 n].     types: NULL, or uint8[n]: the type lfa_download_cells reports for the point's cell.
+ *   n_outside      : NULL, or the number of points outside the grid.
+ * Reads grid arrays only: particles, binning, pressure system, background and the position correction's state are untouched, so a
+ * call between any two stage calls is legal, in every state lfa_download_cells works in (fresh handle, uploaded grid, after
+ * lfa_p2g, after lfa_time_step). Two calls on the same state write the same bytes. n == 0: LFA_OK, nothing written but
+ * *n_outside = 0. LFA_E_INVALID: n >= 2^32, a NULL array with n > 0, cell_size unset. LFA_E_UNSUPPORTED, before anything is touched,
+ * on a slab decomposition (the freshness of the ghost layers would make the call a collective). */
+int lfa_sample_velocity(lfa_sim *s, const double *xyz, uint64_t n, double *velocity, uint8_t *types, uint64_t *n_outside);
+/* Device milliseconds of the kernel of the last lfa_sample_velocity (HIP events on the handle's stream; not the copies).
+ * LFA_E_INVALID when none has run on the device. */
+int lfa_sample_velocity_time(lfa_sim *s, double *ms);
 /* Synthetic dam-break block [lo,hi) in cells, 8 jittered particles per cell, generated on the device; bit-identical
  * to libfluid_amd/scenes.py:seed_block. */
 int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_t seed);
@@ -556,6 +584,26 @@ int lfa_mesher_boundary_size(lfa_mesher *m, uint64_t *n_cells, uint64_t *n_trian
 int lfa_mesher_download_boundary(lfa_mesher *m, uint8_t *cases, double *face);
 int lfa_mesher_window_normals(lfa_mesher *m, const uint8_t *cases_above, const double *face_above, uint64_t n_triangles_above);
 int lfa_mesher_window_normals_from(lfa_mesher *m, lfa_mesher *above);
+/* One velocity per vertex of the mesh just extracted: lfa_sample_velocity (above: simulation::_transfer_from_grid_pic,
+ * src/simulation.cpp:447-461; mac_grid::get_face_samples, src/mac_grid.cpp:42-112; trilerp, include/fluid/misc.h:20-36) of the
+ * simulation `s` at the fp64 vertex positions this handle holds on the device - what a renderer needs to motion-blur the surface.
+ * No position crosses PCIe; the result equals lfa_sample_velocity on the positions of lfa_mesher_download_mesh bit for bit.
+ *   lfa_mesher_vertex_velocities   : computes them into a per-vertex buffer kept for the download; *n_outside (or NULL): vertices
+ *                                    outside the simulation's box (the mesher's grid may be larger), which get zeros. Ordered
+ *                                    after everything queued on the simulation's stream, like lfa_mesher_sample_sim. Needs a
+ *                                    current mesh (LFA_E_INVALID unless lfa_mesher_marching_cubes has succeeded since the values
+ *                                    were last sampled or uploaded); an empty mesh is LFA_OK. LFA_E_INVALID when the handles live
+ *                                    on different devices; LFA_E_UNSUPPORTED, nothing touched, when `s` is a slab decomposition.
+ *                                    On a z-window: the vertices the window owns; the windows' results, concatenated in z order,
+ *                                    are the whole grid's. lfa_mesher_rebase changes nothing.
+ *   lfa_mesher_download_velocities : double[3 nv] in the vertex order of lfa_mesher_download_mesh; LFA_E_INVALID without a
+ *                                    preceding lfa_mesher_vertex_velocities for the current mesh (the velocities go stale exactly
+ *                                    where the normals do); an empty mesh writes nothing.
+ *   lfa_mesher_velocities_time     : device time of the last lfa_mesher_vertex_velocities (HIP events, milliseconds)
+ * The buffer (24 B per vertex) exists from the first request on. */
+int lfa_mesher_vertex_velocities(lfa_mesher *m, lfa_sim *s, uint64_t *n_outside);
+int lfa_mesher_download_velocities(lfa_mesher *m, double *velocity);
+int lfa_mesher_velocities_time(lfa_mesher *m, double *ms);
 
 /* -- measurement --------------------------------------------------------------------------------------------- */
 /* Per-stage device time of the last lfa_step_hot, measured with HIP events on the handle's stream (milliseconds):

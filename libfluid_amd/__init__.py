@@ -95,6 +95,8 @@ SIGNATURES = {
     "lfa_frame_stats": (_int, [_vp, C.POINTER(FrameStats), _vp]),
     "lfa_frame_stats_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_download_positions": (_int, [_vp, _vp, _u64]),
+    "lfa_sample_velocity": (_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "lfa_sample_velocity_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_seed_sphere": (_int, [_vp, _vp, _dbl, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
@@ -166,6 +168,9 @@ SIGNATURES = {
     "lfa_mesher_download_boundary": (_int, [_vp, _vp, _vp]),
     "lfa_mesher_window_normals": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_mesher_window_normals_from": (_int, [_vp, _vp]),
+    "lfa_mesher_vertex_velocities": (_int, [_vp, _vp, C.POINTER(_u64)]),
+    "lfa_mesher_download_velocities": (_int, [_vp, _vp]),
+    "lfa_mesher_velocities_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_clear_sources": (_int, [_vp]),
     "lfa_add_source": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _int]),
     "lfa_update_sources": (_int, [_vp, C.POINTER(_u64)]),
@@ -475,6 +480,21 @@ class Mesher:
         self.compute_window_normals(above)
         return self.download_normals()
 
+    def vertex_velocities(self, sim):
+        """(float64[nv,3], n_outside): the grid velocity of `sim` (Sim.sample_velocity) at the vertices of the mesh of the last
+        marching_cubes(), sampled from the positions the device holds (lfa_mesher_vertex_velocities)."""
+        n_out = _u64(0)
+        self._chk(self.lib.lfa_mesher_vertex_velocities(self.h, sim.h, C.byref(n_out)))
+        out = np.empty((getattr(self, "_counts", (0, 0))[0], 3), dtype=np.float64)
+        self._chk(self.lib.lfa_mesher_download_velocities(self.h, _ptr(out)))
+        return out, n_out.value
+
+    def velocities_ms(self):
+        """Device time of the last vertex_velocities() (lfa_mesher_velocities_time)."""
+        ms = _dbl()
+        self._chk(self.lib.lfa_mesher_velocities_time(self.h, C.byref(ms)))
+        return ms.value
+
     def generate_mesh(self, points, r, normals=False):
         """(positions, indices), and the vertex normals behind them when `normals` is set."""
         self.sample(points, r)
@@ -614,6 +634,23 @@ class Sim:
         out = np.empty((n, 3), dtype=np.float64)
         self._chk(self.lib.lfa_download_positions(self.h, _ptr(out), n))
         return out
+
+    def sample_velocity(self, points, types=False):
+        """velocity float64[n, 3][, types uint8[n]], n_outside: the grid's velocity at world positions float64[n, 3] - what the PIC
+        transfer would give a particle there, on the grid cells() would return (lfa_sample_velocity)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        vel = np.empty((n, 3), dtype=np.float64)
+        typ = np.empty(n, dtype=np.uint8) if types else None
+        n_out = _u64(0)
+        self._chk(self.lib.lfa_sample_velocity(self.h, _ptr(pts), n, _ptr(vel), None if typ is None else _ptr(typ), C.byref(n_out)))
+        return (vel, typ, n_out.value) if types else (vel, n_out.value)
+
+    def sample_velocity_ms(self):
+        """Device milliseconds of the kernel of the last sample_velocity() (lfa_sample_velocity_time)."""
+        out = C.c_double(0.0)
+        self._chk(self.lib.lfa_sample_velocity_time(self.h, C.byref(out)))
+        return out.value
 
     @property
     def num_particles(self):

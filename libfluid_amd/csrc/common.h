@@ -290,6 +290,9 @@ struct lfa_sim {
 	double *frame_part = nullptr;
 	hipEvent_t frame_ev[2] = {nullptr, nullptr};
 	bool frame_timed = false;
+	// velocity sampling (sample.hip): the events around the kernel of the last lfa_sample_velocity
+	hipEvent_t sample_ev[2] = {nullptr, nullptr};
+	bool sample_timed = false;
 
 	// timing
 	bool timing = false;
@@ -341,6 +344,47 @@ __host__ __device__ inline uint64_t raw_from_blocked(const GridDims &g, uint32_t
 	int c[3];
 	cell_coords(g, b, c);
 	return (uint64_t)c[0] + (uint64_t)g.nx * ((uint64_t)c[1] + (uint64_t)g.ny * (uint64_t)c[2]);
+}
+
+// ---------------------------------------------------------------------------------------------------- a cell's value
+/// The grid as a host sees it (lfa_download_cells). Grid kernels only touch the processed (dilated) tile set; every other tile is
+/// implicit: its value is the base (0 after a P2G, the stored value after an explicit upload) plus the background `bg` = gravity
+/// accumulated since then (src/simulation.cpp:72-78 adds g*dt to EVERY cell). ONE statement of that rule: the export
+/// (core.hip: k_export_cells) and the velocity sampling (sample.hip) both read a cell through cell_tile_rule / cell_velocity /
+/// cell_type, and both get their view from lfa_cell_view.
+struct CellView {
+	const float *f[3];  // u, v, w (blocked layout)
+	const uint8_t *ctype, *solid;
+	const uint32_t *tile_flag;
+	int have_dilated, explicit_base;
+	double bg[3];
+};
+enum { CELL_STORED = 0, CELL_BASE_PLUS_BG = 1, CELL_BG = 2 };
+/// Which of the three cases holds for the cells of `tile`.
+__device__ inline int cell_tile_rule(const CellView &c, uint32_t tile) {
+	if (c.have_dilated && c.tile_flag[tile] != 0) return CELL_STORED;
+	return c.explicit_base ? CELL_BASE_PLUS_BG : CELL_BG;
+}
+/// Component `comp` of the velocity of the cell with blocked index b, under its tile's rule.
+__device__ inline double cell_velocity(const CellView &c, int rule, uint32_t b, int comp) {
+	if (rule == CELL_STORED) return (double)c.f[comp][b];
+	if (rule == CELL_BASE_PLUS_BG) return (double)c.f[comp][b] + c.bg[comp];
+	return c.bg[comp];
+}
+__device__ inline uint8_t cell_type(const CellView &c, int rule, uint32_t b) {
+	return rule == CELL_BG ? (uint8_t)(c.solid[b] ? CT_SOLID : CT_AIR) : (uint8_t)(c.ctype[b] & 7);
+}
+/// The view of the handle's current state on the fields u, v, w (`old`: FLIP's old grid, which carries no background).
+inline CellView lfa_cell_view(const lfa_sim *s, const float *u, const float *v, const float *w, bool old) {
+	CellView c;
+	c.f[0] = u; c.f[1] = v; c.f[2] = w;
+	c.ctype = s->ctype;
+	c.solid = s->solid;
+	c.tile_flag = s->grid_valid ? s->grid_flag : s->tile_flag;
+	c.have_dilated = (s->grid_valid || s->binned) ? 1 : 0;
+	c.explicit_base = s->grid_valid ? 0 : 1;
+	for (int k = 0; k < 3; ++k) c.bg[k] = old ? 0.0 : s->bg[k];
+	return c;
 }
 
 // ---------------------------------------------------------------------------------------------------- particle ingest
@@ -518,6 +562,10 @@ int lfa_c_home_restore(lfa_sim *s);         // C back from its home array into t
 int lfa_c_home_ensure(lfa_sim *s, size_t n);  // capacity of the home array (keeps the entries of the resident particles)
 int lfa_ensure_io(lfa_sim *s, size_t bytes);
 int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot);  // place of every record among the resident ones (core.hip; nullptr: dense)
+/// sample.hip: zeroes *n_outside_dev and queues k_sample_velocity on `stream` for n < 2^32 positions that are on the device: 3 n
+/// velocities, n type bytes unless `types` is null, the count of points outside the grid. Reads the handle's grid arrays only.
+int lfa_sample_velocity_launch(lfa_sim *s, hipStream_t stream, const double *xyz, size_t n, double *velocity, uint8_t *types,
+                               uint32_t *n_outside_dev);
 int lfa_pcg_alloc(lfa_sim *s);
 int lfa_number_unknowns(lfa_sim *s);
 

@@ -371,6 +371,8 @@ extern "C" void lfa_destroy(lfa_sim *s) {
 	lfa_pool_nosync_end();
 	for (hipEvent_t e : s->frame_ev)
 		if (e) (void)hipEventDestroy(e);
+	for (hipEvent_t e : s->sample_ev)
+		if (e) (void)hipEventDestroy(e);
 	// streams, events and the pinned page are parked for the next lfa_create on this device (a handle whose creation failed
 	// half way is torn down instead)
 	if (s->stream && s->stream2 && s->stream3 && s->ev_fork && s->ev_join && s->ev_cfork && s->ev_cjoin && s->h_pinned) {
@@ -852,29 +854,18 @@ struct CellAos {
 	uint8_t pad[7];
 };
 
-/// dense x-fastest 32-B AoS <- blocked fp32 SoA. Grid kernels only touch the processed (dilated) tile set; every other
-/// tile is implicit: its value is the base (0 after a P2G, the stored value after an explicit upload) plus the
-/// background `bg` = gravity accumulated since then (src/simulation.cpp:72-78 adds g*dt to EVERY cell).
-__global__ void k_export_cells(CellAos *out, GridDims g, size_t nc, const float *u, const float *v, const float *w,
-                               const uint8_t *ctype, const uint8_t *solid, const uint32_t *tile_flag, int have_dilated,
-                               int explicit_base, double bgx, double bgy, double bgz) {
+/// dense x-fastest 32-B AoS <- blocked fp32 SoA; a cell's value is the rule of common.h (CellView).
+__global__ void k_export_cells(CellAos *out, GridDims g, size_t nc, CellView cv) {
 	size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= nc) return;
 	int x = (int)(r % g.nx), y = (int)((r / g.nx) % g.ny), z = (int)(r / ((size_t)g.nx * g.ny));
 	uint32_t b = blocked_index(g, x, y, z);
 	CellAos c;
 	memset(&c, 0, sizeof c);
-	bool active = have_dilated && tile_flag[b >> 9] != 0;
-	if (active) {
-		c.vel[0] = (double)u[b]; c.vel[1] = (double)v[b]; c.vel[2] = (double)w[b];
-		c.type = ctype[b] & 7;
-	} else if (explicit_base) {
-		c.vel[0] = (double)u[b] + bgx; c.vel[1] = (double)v[b] + bgy; c.vel[2] = (double)w[b] + bgz;
-		c.type = ctype[b] & 7;
-	} else {
-		c.vel[0] = bgx; c.vel[1] = bgy; c.vel[2] = bgz;
-		c.type = solid[b] ? CT_SOLID : CT_AIR;
-	}
+	const int rule = cell_tile_rule(cv, b >> 9);
+#pragma unroll
+	for (int k = 0; k < 3; ++k) c.vel[k] = cell_velocity(cv, rule, b, k);
+	c.type = cell_type(cv, rule, b);
 	out[r] = c;
 }
 
@@ -882,9 +873,7 @@ static int export_cells(lfa_sim *s, void *aos32, const float *u, const float *v,
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_ensure_io(s, s->nc * 32));
 	hipLaunchKernelGGL(k_export_cells, dim3((unsigned)((s->nc + 255) / 256)), dim3(256), 0, s->stream,
-	                   (CellAos *)s->io_buf, s->g, s->nc, u, v, w, s->ctype, s->solid,
-	                   s->grid_valid ? s->grid_flag : s->tile_flag, (s->grid_valid || s->binned) ? 1 : 0,
-	                   s->grid_valid ? 0 : 1, old ? 0.0 : s->bg[0], old ? 0.0 : s->bg[1], old ? 0.0 : s->bg[2]);
+	                   (CellAos *)s->io_buf, s->g, s->nc, lfa_cell_view(s, u, v, w, old));
 	LFA_LAUNCH_CHECK(s);
 	LFA_HIP(s, hipMemcpyAsync(aos32, s->io_buf, s->nc * 32, hipMemcpyDeviceToHost, s->stream));
 	LFA_HIP(s, hipStreamSynchronize(s->stream));

@@ -74,6 +74,12 @@ struct lfa_mesher {
 	uint32_t *b_off = nullptr, *b_flag = nullptr;  // the first cell that contradicts the own layer below it
 	double *b_face = nullptr;      // and that layer's face vectors
 	size_t bfcap = 0;
+	// vertex velocities (lfa_mesher_vertex_velocities): nothing of this exists until the first request
+	double *vvel = nullptr;        // per vertex: the simulation's grid velocity at vpos
+	size_t vvcap = 0;
+	uint32_t *vel_out = nullptr;   // one word: vertices outside the simulation's box
+	bool have_velocities = false;  // `vvel` belongs to the current mesh (stale exactly where the normals are)
+	hipEvent_t vel_ev[2] = {nullptr, nullptr};
 	std::string err;
 };
 
@@ -668,10 +674,12 @@ extern "C" void lfa_mesher_destroy(lfa_mesher *m) {
 	(void)hipSetDevice(m->device);
 	if (m->stream) (void)hipStreamSynchronize(m->stream);
 	void *ptrs[] = {m->ids, m->values, m->cell_start, m->cell_fill, m->order, m->pos, m->spos, m->blk_flag, m->vcount, m->icount, m->created, m->occ, m->blk,
-	                m->vpos, m->vidx, m->face, m->vnorm, m->vbelow, m->b_cases, m->b_off, m->b_flag, m->b_face};
+	                m->vpos, m->vidx, m->face, m->vnorm, m->vbelow, m->b_cases, m->b_off, m->b_flag, m->b_face, m->vvel, m->vel_out};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	for (hipEvent_t e : m->nrm_ev)
+		if (e) (void)hipEventDestroy(e);
+	for (hipEvent_t e : m->vel_ev)
 		if (e) (void)hipEventDestroy(e);
 	if (m->stream) (void)hipStreamDestroy(m->stream);
 	delete m;
@@ -707,6 +715,7 @@ static int sample_device_positions(lfa_mesher *m, const double *dpos, uint64_t n
 	MSH_HIP(m, hipGetLastError());
 	m->have_mesh = false;
 	m->have_normals = false;
+	m->have_velocities = false;
 	m->have_face = false;
 	return LFA_OK;
 }
@@ -817,6 +826,7 @@ extern "C" int lfa_mesher_upload_values(lfa_mesher *m, const double *values) {
 	MSH_HIP(m, hipStreamSynchronize(m->stream));
 	m->have_mesh = false;
 	m->have_normals = false;
+	m->have_velocities = false;
 	m->have_face = false;
 	return LFA_OK;
 }
@@ -826,6 +836,7 @@ extern "C" int lfa_mesher_marching_cubes(lfa_mesher *m, uint64_t *n_vertices, ui
 	MSH_HIP(m, hipSetDevice(m->device));
 	m->have_mesh = false;  // until this extraction has succeeded: a failure half way leaves no mesh, not a mix of two
 	m->have_normals = false;
+	m->have_velocities = false;
 	m->have_face = false;
 	m->rebased = 0;
 	const MeshGrid g = make_grid(m);
@@ -906,6 +917,60 @@ extern "C" int lfa_mesher_download_normals(lfa_mesher *m, double *normals) {
 		MSH_HIP(m, hipMemcpyAsync(normals, m->vnorm, (size_t)m->n_vertices * 24, hipMemcpyDeviceToHost, m->stream));
 		MSH_HIP(m, hipStreamSynchronize(m->stream));
 	}
+	return LFA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- vertex velocities
+/// The simulation's grid velocity (sample.hip: lfa_sample_velocity's kernel) at the vertices this handle holds in vpos: no position
+/// crosses PCIe. Ordered behind everything queued on the simulation's stream, like lfa_mesher_sample_sim.
+extern "C" int lfa_mesher_vertex_velocities(lfa_mesher *m, lfa_sim *s, uint64_t *n_outside) {
+	if (!m || !s) return LFA_E_INVALID;
+	if (s->dist) return mfail(m, LFA_E_UNSUPPORTED, "lfa_mesher_vertex_velocities: not on a slab decomposition (the ghost layers would make it a collective)");
+	if (s->device != m->device) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: handles live on different devices");
+	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: no current mesh, call lfa_mesher_marching_cubes first");
+	if (!(s->prm.cell_size > 0.0)) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: the simulation's cell_size is unset");
+	if (m->n_vertices >= (1ull << 32)) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: 2^32 vertices or more");
+	MSH_HIP(m, hipSetDevice(m->device));
+	m->have_velocities = false;
+	const size_t nv = (size_t)m->n_vertices;
+	int rc = grow(m, &m->vvel, &m->vvcap, nv ? nv : 1, 24);
+	if (rc != LFA_OK) return rc;
+	if (!m->vel_out) MSH_HIP(m, hipMalloc(&m->vel_out, 4));
+	for (hipEvent_t &e : m->vel_ev)
+		if (!e) MSH_HIP(m, hipEventCreate(&e));
+	MSH_HIP(m, hipStreamSynchronize(s->stream));
+	MSH_HIP(m, hipEventRecord(m->vel_ev[0], m->stream));
+	rc = lfa_sample_velocity_launch(s, m->stream, m->vpos, nv, m->vvel, nullptr, m->vel_out);
+	if (rc != LFA_OK) return mfail(m, rc, lfa_last_error(s));
+	MSH_HIP(m, hipEventRecord(m->vel_ev[1], m->stream));
+	uint32_t count = 0;
+	MSH_HIP(m, hipMemcpyAsync(&count, m->vel_out, 4, hipMemcpyDeviceToHost, m->stream));
+	MSH_HIP(m, hipStreamSynchronize(m->stream));
+	m->have_velocities = true;
+	if (n_outside) *n_outside = count;
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_download_velocities(lfa_mesher *m, double *velocity) {
+	if (!m) return LFA_E_INVALID;
+	if (!m->have_mesh || !m->have_velocities)
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_download_velocities: call lfa_mesher_vertex_velocities for the current mesh first");
+	MSH_HIP(m, hipSetDevice(m->device));
+	if (velocity && m->n_vertices) {
+		MSH_HIP(m, hipMemcpyAsync(velocity, m->vvel, (size_t)m->n_vertices * 24, hipMemcpyDeviceToHost, m->stream));
+		MSH_HIP(m, hipStreamSynchronize(m->stream));
+	}
+	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_velocities_time(lfa_mesher *m, double *ms) {
+	if (!m || !ms) return LFA_E_INVALID;
+	if (!m->have_mesh || !m->have_velocities)
+		return mfail(m, LFA_E_INVALID, "lfa_mesher_velocities_time: call lfa_mesher_vertex_velocities for the current mesh first");
+	MSH_HIP(m, hipSetDevice(m->device));
+	float f = 0.0f;
+	MSH_HIP(m, hipEventElapsedTime(&f, m->vel_ev[0], m->vel_ev[1]));
+	*ms = (double)f;
 	return LFA_OK;
 }
 

@@ -61,6 +61,38 @@ namespace fluid_amd {
 			return _status == LFA_OK ? _extract(true) : (_error = lfa_mesher_last_error(_dev), out);
 		}
 
+		/// One velocity per vertex of the mesh of the last generate_mesh* call, in the order of its positions: sim.sample_velocity at
+		/// the vertex positions the device still holds (lfa_mesher_vertex_velocities; no position crosses PCIe). Vertices outside the
+		/// simulation's box get zeros and are counted in *n_outside. mesh_t is the reference's type and gains no member.
+		[[nodiscard]] std::vector<vec3d> vertex_velocities(simulation &sim, std::size_t *n_outside = nullptr) {
+			std::vector<vec3d> out;
+			if (n_outside) *n_outside = 0;
+			if (!_dev || !sim.device_handle()) {
+				_status = LFA_E_INVALID;
+				_error = "vertex_velocities: no mesh (call generate_mesh first) or no simulation on the device";
+				return out;
+			}
+			sim.sample_velocity({});  // (brings the device up to date with edits made through sim.grid())
+			if (sim.last_status() < 0) {  // the device's grid is not the one sim.grid() shows: nothing is sampled
+				_status = sim.last_status();
+				_error = "vertex_velocities: the simulation could not bring its device up to date: " + sim.last_error();
+				return out;
+			}
+			std::uint64_t outside = 0;
+			_status = lfa_mesher_vertex_velocities(_dev, sim.device_handle(), &outside);
+			if (_status == LFA_OK) {
+				out.resize(_n_vertices);
+				_status = lfa_mesher_download_velocities(_dev, out.empty() ? nullptr : &out[0].x);
+			}
+			if (_status != LFA_OK) {
+				_error = lfa_mesher_last_error(_dev);
+				out.clear();
+				return out;
+			}
+			if (n_outside) *n_outside = static_cast<std::size_t>(outside);
+			return out;
+		}
+
 		vec3d grid_offset;
 		double cell_size = 0.0, particle_extent = 0.5;
 		std::size_t cell_radius = 2;
@@ -77,6 +109,7 @@ namespace fluid_amd {
 		std::size_t _dev_radius = 0;
 		int _status = LFA_OK;
 		std::string _error;
+		std::size_t _n_vertices = 0;  // of the mesh the device holds
 
 		void _release() {
 			if (_dev) lfa_mesher_destroy(_dev);
@@ -110,6 +143,7 @@ namespace fluid_amd {
 				return out;
 			}
 			out.positions.resize(nv);
+			_n_vertices = nv;
 			std::vector<std::uint64_t> idx(ni);
 			_status = lfa_mesher_download_mesh(_dev, reinterpret_cast<double *>(out.positions.data()), idx.data());
 			if (_status != LFA_OK) _error = lfa_mesher_last_error(_dev);

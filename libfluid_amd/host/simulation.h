@@ -179,6 +179,13 @@ namespace fluid_amd {
 		frame_summary frame_stats(bool with_occupation = true);
 		/// `position` of every particle, in the order of particles() (the GridNode's cache loop, grid_node.cpp:356-364).
 		void positions(std::vector<vec3d> &out);
+		/// The grid's velocity at world positions of the caller's choosing (lfa_sample_velocity): what the PIC transfer
+		/// (src/simulation.cpp:447-461) would give a particle there, bit for bit, on the grid that grid() would show at that moment -
+		/// without downloading it (the testbed's grid_vels copy, testbed/main.cpp:70-78; velocities for motion blur). An edit made
+		/// through grid() that has not reached the device yet is uploaded first. `types`: the cell type at every point (0 outside the
+		/// grid); `n_outside`: the points outside the grid, which get zeros. Never throws: see last_status() / last_error().
+		std::vector<vec3d> sample_velocity(const std::vector<vec3d> &points, std::vector<unsigned char> *types = nullptr,
+		                                   std::size_t *n_outside = nullptr);
 
 		// callbacks, in calling order (include/fluid/simulation.h:150-175)
 		std::function<void(double)> pre_time_step_callback, post_advection_callback,
@@ -316,8 +323,8 @@ namespace fluid_amd {
 			if (rc < 0) { _status = rc; _error = _dev ? lfa_last_error(_dev) : lfa_last_error(nullptr); return false; }
 			return true;
 		}
-		bool _flush_host_edits();
-		bool _device_current();
+		bool _flush_host_edits(bool grid_too = false);
+		bool _device_current(bool grid_too = false);
 		bool _push_sources();
 		void _device_advanced() { _host_stale = true; _grid_stale = true; }
 		bool _push_params();
@@ -529,8 +536,9 @@ namespace fluid_amd {
 
 	/// Brings the device up to date with whatever the host did through particles() / grid() / the seeding functions since the last
 	/// device stage. Between steps only the solid mask of the grid matters (the P2G rebuilds velocities and air / fluid types);
-	/// inside a staged step an edited grid is uploaded whole and edited particles are re-uploaded and re-binned.
-	inline bool simulation::_flush_host_edits() {
+	/// inside a staged step - or for a caller that reads the grid on the device (`grid_too`: sample_velocity) - an edited grid is
+	/// uploaded whole; inside a staged step edited particles are re-uploaded and re-binned.
+	inline bool simulation::_flush_host_edits(bool grid_too) {
 		if (_particles_handed_out && !_host_stale) {
 			const std::uint64_t before = _particles_hash;
 			_rehash_particles();
@@ -542,9 +550,10 @@ namespace fluid_amd {
 			_rehash_grid();
 			if (_grid_solid_hash != solid_before) _solids_dirty = true;
 			if (_solids_dirty && !_take_back_correction()) return false;  // the correction collides against the solid cells
-			if (_in_step && (_grid_vel_hash != vel_before || _grid_solid_hash != solid_before)) {
+			if ((_in_step || grid_too) && (_grid_vel_hash != vel_before || _grid_solid_hash != solid_before)) {
 				if (!_ok(lfa_upload_cells(_dev, detail::cell_data(_grid.grid())))) return false;
 				_solids_dirty = false;
+				if (!_in_step) _grid_stale = true;  // the device stores fp32: grid() shows what it holds now, not what was handed in
 			}
 			_grid_handed_out = false;
 		}
@@ -568,10 +577,10 @@ namespace fluid_amd {
 
 	/// The device must hold what the host has edited, and show the particles where the reference's step order has them (a
 	/// correction running ahead is taken back, as for particles()).
-	inline bool simulation::_device_current() {
+	inline bool simulation::_device_current(bool grid_too) {
 		if (_status < 0) return false;
 		if (!_dev) { _status = LFA_E_NO_DEVICE; _error = "no device handle: resize() failed or was not called (there is no CPU fallback)"; return false; }
-		return _push_params() && _take_back_correction() && _flush_host_edits();
+		return _push_params() && _take_back_correction() && _flush_host_edits(grid_too);
 	}
 	inline simulation::frame_summary simulation::frame_stats(bool with_occupation) {
 		frame_summary r{};
@@ -588,6 +597,26 @@ namespace fluid_amd {
 		if (!_device_current()) return;
 		out.resize(static_cast<std::size_t>(lfa_num_particles(_dev)));
 		if (!_ok(lfa_download_positions(_dev, out.empty() ? nullptr : &out[0].x, out.size()))) out.clear();
+	}
+
+	inline std::vector<vec3d> simulation::sample_velocity(const std::vector<vec3d> &points, std::vector<unsigned char> *types,
+	                                                      std::size_t *n_outside) {
+		static_assert(sizeof(vec3d) == 24, "vec3d must be three packed doubles");
+		std::vector<vec3d> out;
+		if (types) types->clear();
+		if (n_outside) *n_outside = 0;
+		if (!_device_current(true)) return out;
+		out.resize(points.size());
+		if (types) types->resize(points.size());
+		std::uint64_t outside = 0;
+		if (!_ok(lfa_sample_velocity(_dev, points.empty() ? nullptr : &points[0].x, points.size(), out.empty() ? nullptr : &out[0].x,
+		                             types && !types->empty() ? types->data() : nullptr, &outside))) {
+			out.clear();
+			if (types) types->clear();
+			return out;
+		}
+		if (n_outside) *n_outside = static_cast<std::size_t>(outside);
+		return out;
 	}
 
 	inline void simulation::time_step(double dt) {
