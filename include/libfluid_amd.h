@@ -185,8 +185,37 @@ int lfa_download_positions(lfa_sim *s, double *xyz, uint64_t n);
  * call between any two stage calls is legal, in every state lfa_download_cells works in (fresh handle, uploaded grid, after
  * lfa_p2g, after lfa_time_step). Two calls on the same state write the same bytes. n == 0: LFA_OK, nothing written but
  * *n_outside = 0. LFA_E_INVALID: n >= 2^32, a NULL array with n > 0, cell_size unset. LFA_E_UNSUPPORTED, before anything is touched,
- * on a slab decomposition (the freshness of the ghost layers would make the call a collective). */
+ * on a slab decomposition (the freshness of the ghost layers makes the call a collective: lfa_sample_velocity_collective). */
 int lfa_sample_velocity(lfa_sim *s, const double *xyz, uint64_t n, double *velocity, uint8_t *types, uint64_t *n_outside);
+/* The same on a slab decomposition. COLLECTIVE: every rank of the job makes the call, a rank with n == 0 too; the lists may differ
+ * from rank to rank (all the same list, each its own, an empty one). A sample block reaches one cell beyond the point's cell, so a
+ * rank answers for the points of its own tile layers once its ghost layers answer like their owners - the call makes them (below).
+ *   owner    : by cell: c = trunc((x - grid_offset) / cell_size), the division above; the rank whose tile layers hold c_z >> 3.
+ *              The inside points are partitioned over the ranks; an outside point belongs to nobody and every rank counts it.
+ *   output   : COMPACT and in input order: index[k] = position in xyz of the k-th point this rank owns (ascending),
+ *              velocity[3 k ..] and types[k] (or NULL) its values. No row is written for a point the rank does not own; capacity =
+ *              the rows index, velocity and types have room for, capacity >= n always suffices. 28 (29) bytes come down per OWNED
+ *              point, 24 go up per point shown.
+ *   counts   : [0] points this rank answered, [1] points outside the grid, [2] inside points that belong to other ranks;
+ *              [0] + [1] + [2] == n.
+ *   value    : what lfa_sample_velocity returns on a single-domain handle whose lfa_download_cells is the ranks' downloads
+ *              stitched by owned z-range, bit for bit, types included. Two calls on the same state write the same bytes.
+ * Order inside the call:
+ *   1. the handle's state, the same on every rank by construction: cell_size set, and binned by a collective lfa_hash_particles;
+ *      otherwise LFA_E_INVALID (the message names lfa_hash_particles) on every rank, and no message is sent.
+ *   2. the ghost refresh, two transport calls: the rule a cell's value follows, per tile of the boundary layers, as its OWNER's
+ *      state gives it (stored / stored base plus background / background alone: the ranks' states can differ, e.g. after a
+ *      collective seeding that left particles on some ranks only), then u, v, w and the cell types of the tiles whose rule reads
+ *      them. What stays the caller's: solid cells and the background are the same on every rank, and after lfa_upload_cells the
+ *      ghost layers' base values equal their owners' if every rank uploaded the same whole grid.
+ *   3. this rank's arguments and work. LFA_E_INVALID here - a NULL xyz / index / velocity with n > 0, n >= 2^32, capacity below
+ *      counts[0] - is this rank's alone: counts is filled (zeros when the list itself is unusable), nothing else is written, the
+ *      peers' calls complete unharmed, and a repeat is a NEW collective call that every rank has to make again.
+ * On a single domain the call is local (no message, every layer owned): index lists the inside points, so one host code serves 1 and
+ * N ranks. lfa_sample_velocity_time then reports the device time from the count pass to the write pass (the read-back of the two
+ * totals between them included, the refresh and the copies not). */
+int lfa_sample_velocity_collective(lfa_sim *s, const double *xyz, uint64_t n, uint32_t *index, double *velocity, uint8_t *types,
+                                   uint64_t capacity, uint64_t counts[3]);
 /* Device milliseconds of the kernel of the last lfa_sample_velocity (HIP events on the handle's stream; not the copies).
  * LFA_E_INVALID when none has run on the device. */
 int lfa_sample_velocity_time(lfa_sim *s, double *ms);
@@ -593,15 +622,27 @@ int lfa_mesher_window_normals_from(lfa_mesher *m, lfa_mesher *above);
  *                                    after everything queued on the simulation's stream, like lfa_mesher_sample_sim. Needs a
  *                                    current mesh (LFA_E_INVALID unless lfa_mesher_marching_cubes has succeeded since the values
  *                                    were last sampled or uploaded); an empty mesh is LFA_OK. LFA_E_INVALID when the handles live
- *                                    on different devices; LFA_E_UNSUPPORTED, nothing touched, when `s` is a slab decomposition.
+ *                                    on different devices; LFA_E_UNSUPPORTED, nothing touched, when `s` is a slab decomposition (below).
  *                                    On a z-window: the vertices the window owns; the windows' results, concatenated in z order,
  *                                    are the whole grid's. lfa_mesher_rebase changes nothing.
+ *   lfa_mesher_vertex_velocities_collective : the same when `s` is a slab decomposition. COLLECTIVE in `s`: every rank makes the
+ *                                    call, with the state checks and the ghost refresh of lfa_sample_velocity_collective first
+ *                                    (steps 1 and 2 there); what follows - the mesher's own checks above included - is the rank's
+ *                                    alone. The result stays dense, one row per vertex. A window's vertices on its top plane lie
+ *                                    in the cell layer of the rank above, so a rank answers by REACH, not by ownership: every
+ *                                    vertex whose cell z lies in [max(0, 8 lo - 7), min(nz, 8 hi + 7)) for the rank's tile layers
+ *                                    [lo, hi) - the sample block of such a cell stays inside the own and the ghost layers.
+ *                                    counts: [0] vertices outside the simulation's box, [1] vertices inside it but beyond this
+ *                                    rank's reach; both kinds get +0.0. With the windows [8 lo, min(8 hi, nz)) on the
+ *                                    simulation's own grid counts[1] == 0 on every rank, and the windows' results, concatenated
+ *                                    in z order, are the job's. On a single domain it equals lfa_mesher_vertex_velocities.
  *   lfa_mesher_download_velocities : double[3 nv] in the vertex order of lfa_mesher_download_mesh; LFA_E_INVALID without a
  *                                    preceding lfa_mesher_vertex_velocities for the current mesh (the velocities go stale exactly
  *                                    where the normals do); an empty mesh writes nothing.
  *   lfa_mesher_velocities_time     : device time of the last lfa_mesher_vertex_velocities (HIP events, milliseconds)
  * The buffer (24 B per vertex) exists from the first request on. */
 int lfa_mesher_vertex_velocities(lfa_mesher *m, lfa_sim *s, uint64_t *n_outside);
+int lfa_mesher_vertex_velocities_collective(lfa_mesher *m, lfa_sim *s, uint64_t counts[2]);
 int lfa_mesher_download_velocities(lfa_mesher *m, double *velocity);
 int lfa_mesher_velocities_time(lfa_mesher *m, double *ms);
 

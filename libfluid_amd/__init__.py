@@ -96,6 +96,7 @@ SIGNATURES = {
     "lfa_frame_stats_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_download_positions": (_int, [_vp, _vp, _u64]),
     "lfa_sample_velocity": (_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "lfa_sample_velocity_collective": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64 * 3)]),
     "lfa_sample_velocity_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
@@ -169,6 +170,7 @@ SIGNATURES = {
     "lfa_mesher_window_normals": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_mesher_window_normals_from": (_int, [_vp, _vp]),
     "lfa_mesher_vertex_velocities": (_int, [_vp, _vp, C.POINTER(_u64)]),
+    "lfa_mesher_vertex_velocities_collective": (_int, [_vp, _vp, C.POINTER(_u64 * 2)]),
     "lfa_mesher_download_velocities": (_int, [_vp, _vp]),
     "lfa_mesher_velocities_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_clear_sources": (_int, [_vp]),
@@ -489,6 +491,16 @@ class Mesher:
         self._chk(self.lib.lfa_mesher_download_velocities(self.h, _ptr(out)))
         return out, n_out.value
 
+    def vertex_velocities_collective(self, sim):
+        """(float64[nv,3], (n_outside, n_beyond_reach)): vertex_velocities() when `sim` is a slab decomposition. COLLECTIVE in `sim`:
+        every rank makes the call; a rank answers the vertices within its reach, the others get +0.0 and are counted
+        (lfa_mesher_vertex_velocities_collective)."""
+        counts = (_u64 * 2)()
+        self._chk(self.lib.lfa_mesher_vertex_velocities_collective(self.h, sim.h, C.byref(counts)))
+        out = np.empty((getattr(self, "_counts", (0, 0))[0], 3), dtype=np.float64)
+        self._chk(self.lib.lfa_mesher_download_velocities(self.h, _ptr(out)))
+        return out, tuple(int(c) for c in counts)
+
     def velocities_ms(self):
         """Device time of the last vertex_velocities() (lfa_mesher_velocities_time)."""
         ms = _dbl()
@@ -645,6 +657,29 @@ class Sim:
         n_out = _u64(0)
         self._chk(self.lib.lfa_sample_velocity(self.h, _ptr(pts), n, _ptr(vel), None if typ is None else _ptr(typ), C.byref(n_out)))
         return (vel, typ, n_out.value) if types else (vel, n_out.value)
+
+    def sample_velocity_collective(self, points, types=False, capacity=None):
+        """index uint32[k], velocity float64[k, 3][, types uint8[k]], counts: sample_velocity() on a slab decomposition. COLLECTIVE:
+        every rank makes the call (its own list, possibly empty); a rank gets the k points whose cell lies in its tile layers,
+        compact and in input order, index[j] their positions in `points`. counts = (answered here, outside the grid, inside but
+        owned by other ranks). capacity: rows of room (default: len(points), which always suffices); when it is short the call
+        raises on this rank alone and the error carries `counts` (lfa_sample_velocity_collective)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        cap = n if capacity is None else int(capacity)
+        idx = np.empty(cap, dtype=np.uint32)
+        vel = np.empty((cap, 3), dtype=np.float64)
+        typ = np.empty(cap, dtype=np.uint8) if types else None
+        counts = (_u64 * 3)()
+        rc = self.lib.lfa_sample_velocity_collective(self.h, _ptr(pts), n, _ptr(idx), _ptr(vel), None if typ is None else _ptr(typ), cap,
+                                                     C.byref(counts))
+        counts = tuple(int(c) for c in counts)
+        if rc < 0:
+            err = LibfluidError(rc, self.lib.lfa_last_error(self.h).decode())
+            err.counts = counts
+            raise err
+        k = counts[0]
+        return (idx[:k], vel[:k], typ[:k], counts) if types else (idx[:k], vel[:k], counts)
 
     def sample_velocity_ms(self):
         """Device milliseconds of the kernel of the last sample_velocity() (lfa_sample_velocity_time)."""

@@ -356,12 +356,14 @@ struct CellView {
 	const float *f[3];  // u, v, w (blocked layout)
 	const uint8_t *ctype, *solid;
 	const uint32_t *tile_flag;
+	const uint32_t *tile_rule;  // null, or per tile 1 + its rule as the tile's OWNER states it (slabs: sample.hip, lfa_sample_refresh; cell_tile_rule<true>)
 	int have_dilated, explicit_base;
 	double bg[3];
 };
 enum { CELL_STORED = 0, CELL_BASE_PLUS_BG = 1, CELL_BG = 2 };
-/// Which of the three cases holds for the cells of `tile`.
-__device__ inline int cell_tile_rule(const CellView &c, uint32_t tile) {
+/// Which of the three cases holds for the cells of `tile`. OWNER_RULES: the view carries tile_rule, and that decides.
+template <bool OWNER_RULES = false> __device__ inline int cell_tile_rule(const CellView &c, uint32_t tile) {
+	if (OWNER_RULES) return (int)c.tile_rule[tile] - 1;
 	if (c.have_dilated && c.tile_flag[tile] != 0) return CELL_STORED;
 	return c.explicit_base ? CELL_BASE_PLUS_BG : CELL_BG;
 }
@@ -381,6 +383,7 @@ inline CellView lfa_cell_view(const lfa_sim *s, const float *u, const float *v, 
 	c.ctype = s->ctype;
 	c.solid = s->solid;
 	c.tile_flag = s->grid_valid ? s->grid_flag : s->tile_flag;
+	c.tile_rule = nullptr;
 	c.have_dilated = (s->grid_valid || s->binned) ? 1 : 0;
 	c.explicit_base = s->grid_valid ? 0 : 1;
 	for (int k = 0; k < 3; ++k) c.bg[k] = old ? 0.0 : s->bg[k];
@@ -550,6 +553,8 @@ enum {
 	LFA_PIN_RESIDENT = 99,           // lfa_particles_close_holes: resident records
 	LFA_PIN_SOURCE_TOTAL_ALL = 104,  // collective lfa_update_sources_rng: particles the whole job creates ...
 	LFA_PIN_SOURCE_KEPT = 105,       // ... and those of them this rank keeps
+	LFA_PIN_SAMPLE_OWNED = 106,      // lfa_sample_velocity_collective: points this rank owns ...
+	LFA_PIN_SAMPLE_OUTSIDE = 107,    // ... and points outside the grid
 };
 /// The scan, its total (left in *total_dev on the device) read back through h_pinned[slot]: one synchronisation of the stream.
 int lfa_scan_total(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev, int slot, size_t *total);
@@ -562,10 +567,19 @@ int lfa_c_home_restore(lfa_sim *s);         // C back from its home array into t
 int lfa_c_home_ensure(lfa_sim *s, size_t n);  // capacity of the home array (keeps the entries of the resident particles)
 int lfa_ensure_io(lfa_sim *s, size_t bytes);
 int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot);  // place of every record among the resident ones (core.hip; nullptr: dense)
-/// sample.hip: zeroes *n_outside_dev and queues k_sample_velocity on `stream` for n < 2^32 positions that are on the device: 3 n
-/// velocities, n type bytes unless `types` is null, the count of points outside the grid. Reads the handle's grid arrays only.
-int lfa_sample_velocity_launch(lfa_sim *s, hipStream_t stream, const double *xyz, size_t n, double *velocity, uint8_t *types,
-                               uint32_t *n_outside_dev);
+/// sample.hip: zeroes counts_dev[0..1] and queues k_sample_velocity on `stream` for n < 2^32 positions that are on the device: 3 n
+/// velocities and, unless `types` is null, n type bytes. Points whose cell z lies in [z_lo, z_hi) are answered; counts_dev[0]: points
+/// outside the grid, counts_dev[1]: inside points beyond that range (both kinds get +0.0 and type 0). tile_rule: null, or what
+/// lfa_sample_refresh returned. Reads the handle's grid arrays only.
+int lfa_sample_velocity_launch(lfa_sim *s, hipStream_t stream, const double *xyz, size_t n, const uint32_t *tile_rule, int z_lo, int z_hi,
+                               double *velocity, uint8_t *types, uint32_t *counts_dev);
+/// sample.hip, COLLECTIVE on a slab decomposition, local otherwise. First the checks of the handle's state, which is the same on every
+/// rank (cell_size set, binned if slabs; LFA_E_INVALID in the name of `who`, no message sent). Then it makes the ghost tile layers answer like their
+/// owners (one exchange of the rules per tile, one of u, v, w and ctype) and returns the rules (*tile_rule; null on a single domain)
+/// for the view of a sampling kernel. They live at the head of the handle's io buffer, with `room_bytes` of scratch behind them
+/// (*room), until the buffer is next asked for. [*z_lo, *z_hi): the cell layers a sample block of which stays inside the own and
+/// the ghost layers (the REACH of this rank; the whole grid on a single domain).
+int lfa_sample_refresh(lfa_sim *s, const char *who, size_t room_bytes, const uint32_t **tile_rule, void **room, int *z_lo, int *z_hi);
 int lfa_pcg_alloc(lfa_sim *s);
 int lfa_number_unknowns(lfa_sim *s);
 
@@ -618,8 +632,11 @@ enum { LFA_RED_U8 = 0, LFA_RED_F32 = 1, LFA_RED_F64 = 2 };
 inline bool lfa_has_lo(const lfa_sim *s) { return s->dist && s->dist->rank > 0; }
 inline bool lfa_has_hi(const lfa_sim *s) { return s->dist && s->dist->rank + 1 < s->dist->nranks; }
 int lfa_dist_exchange_tile_layers_u32(lfa_sim *s, uint32_t *per_tile);  // own boundary layers -> neighbours' ghost layers
-int lfa_dist_build_halo_lists(lfa_sim *s);
-int lfa_dist_exchange_fields(lfa_sim *s, int nfields, void *const *fields, const int *elem_bytes);
+/// The flagged tiles of the four boundary layers under `flag` (one word per tile): [own first | own last | ghost below | ghost above],
+/// each in its own region of one tile layer of `lists`, their counts in n (core.hip).
+int lfa_dist_build_halo_lists(lfa_sim *s, const uint32_t *flag, int *lists, int n[4]);
+int lfa_dist_exchange_fields(lfa_sim *s, int nfields, void *const *fields, const int *elem_bytes);  // the tiles of halo_tiles / n_halo
+int lfa_dist_exchange_fields_of(lfa_sim *s, const int *lists, const int n[4], int nfields, void *const *fields, const int *elem_bytes);
 int lfa_dist_exchange_p2g_planes(lfa_sim *s, float *stage_all);
 int lfa_dist_exchange_slices(lfa_sim *s, void *vec, int elem_bytes);  // elem_bytes 1, 4 or 8
 /// The same for a whole tile layer of a tile-major array with `tiles_per_layer` tiles per layer (multigrid levels): slice 0 of

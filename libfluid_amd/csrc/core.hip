@@ -1083,21 +1083,6 @@ static int compact_tiles_async(lfa_sim *s, const uint32_t *flag, int lo, int hi,
 	return LFA_OK;
 }
 
-/// Compacts the flagged tiles of [lo, hi) into `list` (ascending tile id); the count is returned through the host.
-static int compact_tiles(lfa_sim *s, const uint32_t *flag, int lo, int hi, int *list, int *slot_of, int *count) {
-	*count = 0;
-	if (hi <= lo) return LFA_OK;
-	uint32_t *total = (uint32_t *)s->pcg_state + 8;
-	LFA_TRY(lfa_exclusive_scan_u32(s, flag + lo, s->tile_scan + lo, (size_t)(hi - lo), total));
-	hipLaunchKernelGGL(k_compact_range, dim3((hi - lo + 255) / 256), dim3(256), 0, s->stream, flag, s->tile_scan - 0,
-	                   list - 0, slot_of, lo, hi, 0);
-	LFA_LAUNCH_CHECK(s);
-	LFA_HIP(s, hipMemcpyAsync(s->h_pinned, total, 4, hipMemcpyDeviceToHost, s->stream));
-	LFA_HIP(s, hipStreamSynchronize(s->stream));
-	*count = (int)s->h_pinned[0];
-	return LFA_OK;
-}
-
 int lfa_c_home_ensure(lfa_sim *s, size_t n) {
 	if (n <= s->c_home_cap) return LFA_OK;
 	const size_t cap = ((n + n / 8) + 1023) & ~(size_t)1023;
@@ -1280,16 +1265,20 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 	return LFA_OK;
 }
 
-/// Processed tiles of the four boundary layers: [own first | own last | ghost below | ghost above], each in its own region of
-/// one tile layer of halo_tiles (the binning builds them itself, with its other lists; this entry point re-builds them alone).
-int lfa_dist_build_halo_lists(lfa_sim *s) {
+/// The flagged tiles of the four boundary layers: [own first | own last | ghost below | ghost above], each in its own region of one
+/// tile layer of `lists`. The binning builds halo_tiles itself, from tile_flag and with its other lists; this builds such lists
+/// alone and under any flags - the velocity sampling's, whose view of the grid may read grid_flag (sample.hip). One synchronisation.
+int lfa_dist_build_halo_lists(lfa_sim *s, const uint32_t *flag, int *lists, int n[4]) {
 	const int L = s->g.ntx * s->g.nty;
 	const int lo[4] = {s->slab_lo * L, (s->slab_hi - 1) * L, (s->slab_lo - 1) * L, s->slab_hi * L};
 	const bool on[4] = {lfa_has_lo(s), lfa_has_hi(s), lfa_has_lo(s), lfa_has_hi(s)};
-	for (int w = 0; w < 4; ++w) {
-		s->n_halo[w] = 0;
-		if (on[w]) LFA_TRY(compact_tiles(s, s->tile_flag, lo[w], lo[w] + L, s->halo_tiles + (size_t)w * L, nullptr, &s->n_halo[w]));
-	}
+	uint32_t *tot = (uint32_t *)s->pcg_state + 26;  // (the binning's slots for its own four)
+	LFA_HIP(s, hipMemsetAsync(tot, 0, 16, s->stream));
+	for (int w = 0; w < 4; ++w)
+		if (on[w]) LFA_TRY(compact_tiles_async(s, flag, lo[w], lo[w] + L, lists + (size_t)w * L, nullptr, tot + w));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 26, tot, 16, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	for (int w = 0; w < 4; ++w) n[w] = (int)s->h_pinned[26 + w];
 	return LFA_OK;
 }
 

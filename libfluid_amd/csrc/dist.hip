@@ -203,6 +203,10 @@ int lfa_dist_exchange_tile_layers_u32(lfa_sim *s, uint32_t *per_tile) {
 
 /// u,v,w,... of the processed tiles of the boundary layers: own layers out, ghost layers in.
 int lfa_dist_exchange_fields(lfa_sim *s, int nfields, void *const *fields, const int *elem_bytes) {
+	return lfa_dist_exchange_fields_of(s, s->halo_tiles, s->n_halo, nfields, fields, elem_bytes);
+}
+/// The same for the tiles of `lists` ([send_lo | send_hi | recv_lo | recv_hi], a region of one tile layer each; n: their counts).
+int lfa_dist_exchange_fields_of(lfa_sim *s, const int *lists, const int n[4], int nfields, void *const *fields, const int *elem_bytes) {
 	if (!s->dist) return LFA_OK;
 	FieldList f;
 	f.n = nfields;
@@ -215,19 +219,16 @@ int lfa_dist_exchange_fields(lfa_sim *s, int nfields, void *const *fields, const
 	const size_t tb = (size_t)f.tile_words * 4;
 	const int Lh = s->g.ntx * s->g.nty;
 	const int off[4] = {0, Lh, 2 * Lh, 3 * Lh};  // (every list has a region of one tile layer: core.hip, the binning)
-	for (int w = 0; w < 4; ++w) LFA_TRY(lfa_dist_ensure_xbuf(s, w, (size_t)s->n_halo[w] * tb));
+	for (int w = 0; w < 4; ++w) LFA_TRY(lfa_dist_ensure_xbuf(s, w, (size_t)n[w] * tb));
 	for (int w = 0; w < 2; ++w)
-		if (s->n_halo[w]) {
-			hipLaunchKernelGGL(k_tiles_copy<true>, dim3(s->n_halo[w]), dim3(256), 0, s->stream, s->halo_tiles + off[w],
-			                   s->n_halo[w], f, (uint32_t *)s->xbuf[w]);
+		if (n[w]) {
+			hipLaunchKernelGGL(k_tiles_copy<true>, dim3(n[w]), dim3(256), 0, s->stream, lists + off[w], n[w], f, (uint32_t *)s->xbuf[w]);
 			LFA_LAUNCH_CHECK(s);
 		}
-	LFA_TRY(s->dist->exchange(s, s->xbuf[0], s->n_halo[0] * tb, s->xbuf[2], s->n_halo[2] * tb, s->xbuf[1],
-	                          s->n_halo[1] * tb, s->xbuf[3], s->n_halo[3] * tb));
+	LFA_TRY(s->dist->exchange(s, s->xbuf[0], n[0] * tb, s->xbuf[2], n[2] * tb, s->xbuf[1], n[1] * tb, s->xbuf[3], n[3] * tb));
 	for (int w = 2; w < 4; ++w)
-		if (s->n_halo[w]) {
-			hipLaunchKernelGGL(k_tiles_copy<false>, dim3(s->n_halo[w]), dim3(256), 0, s->stream, s->halo_tiles + off[w],
-			                   s->n_halo[w], f, (uint32_t *)s->xbuf[w]);
+		if (n[w]) {
+			hipLaunchKernelGGL(k_tiles_copy<false>, dim3(n[w]), dim3(256), 0, s->stream, lists + off[w], n[w], f, (uint32_t *)s->xbuf[w]);
 			LFA_LAUNCH_CHECK(s);
 		}
 	return LFA_OK;

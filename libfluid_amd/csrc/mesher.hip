@@ -77,7 +77,7 @@ struct lfa_mesher {
 	// vertex velocities (lfa_mesher_vertex_velocities): nothing of this exists until the first request
 	double *vvel = nullptr;        // per vertex: the simulation's grid velocity at vpos
 	size_t vvcap = 0;
-	uint32_t *vel_out = nullptr;   // one word: vertices outside the simulation's box
+	uint32_t *vel_out = nullptr;   // two words: vertices outside the simulation's box, vertices inside it but beyond the rank's reach
 	bool have_velocities = false;  // `vvel` belongs to the current mesh (stale exactly where the normals are)
 	hipEvent_t vel_ev[2] = {nullptr, nullptr};
 	std::string err;
@@ -922,33 +922,63 @@ extern "C" int lfa_mesher_download_normals(lfa_mesher *m, double *normals) {
 
 // ---------------------------------------------------------------------------------------------- vertex velocities
 /// The simulation's grid velocity (sample.hip: lfa_sample_velocity's kernel) at the vertices this handle holds in vpos: no position
-/// crosses PCIe. Ordered behind everything queued on the simulation's stream, like lfa_mesher_sample_sim.
-extern "C" int lfa_mesher_vertex_velocities(lfa_mesher *m, lfa_sim *s, uint64_t *n_outside) {
-	if (!m || !s) return LFA_E_INVALID;
-	if (s->dist) return mfail(m, LFA_E_UNSUPPORTED, "lfa_mesher_vertex_velocities: not on a slab decomposition (the ghost layers would make it a collective)");
-	if (s->device != m->device) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: handles live on different devices");
-	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: no current mesh, call lfa_mesher_marching_cubes first");
-	if (!(s->prm.cell_size > 0.0)) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: the simulation's cell_size is unset");
-	if (m->n_vertices >= (1ull << 32)) return mfail(m, LFA_E_INVALID, "lfa_mesher_vertex_velocities: 2^32 vertices or more");
+/// crosses PCIe. Ordered behind everything queued on the simulation's stream, like lfa_mesher_sample_sim. collective: `s` may be a
+/// slab decomposition - the ghost refresh comes first (every rank makes it, whatever becomes of the rank's own call after it), and
+/// the vertices within the rank's reach are answered; counts: [0] outside the simulation's box, [1] inside it but beyond reach.
+static int vertex_velocities(lfa_mesher *m, lfa_sim *s, bool collective, uint64_t counts[2]) {
+	const std::string who = collective ? "lfa_mesher_vertex_velocities_collective" : "lfa_mesher_vertex_velocities";
+	const uint32_t *rule = nullptr;
+	void *room = nullptr;
+	int z_lo = 0, z_hi = s->g.nz;
+	if (collective) {
+		const int rc = lfa_sample_refresh(s, who.c_str(), 0, &rule, &room, &z_lo, &z_hi);
+		if (rc < 0) return mfail(m, rc, lfa_last_error(s));
+	} else if (s->dist) {
+		return mfail(m, LFA_E_UNSUPPORTED, "lfa_mesher_vertex_velocities: not on a slab decomposition (the ghost layers would make it a collective: lfa_mesher_vertex_velocities_collective)");
+	}
+	if (s->device != m->device) return mfail(m, LFA_E_INVALID, (who + ": handles live on different devices").c_str());
+	if (!m->have_mesh) return mfail(m, LFA_E_INVALID, (who + ": no current mesh, call lfa_mesher_marching_cubes first").c_str());
+	if (!(s->prm.cell_size > 0.0)) return mfail(m, LFA_E_INVALID, (who + ": the simulation's cell_size is unset").c_str());
+	if (m->n_vertices >= (1ull << 32)) return mfail(m, LFA_E_INVALID, (who + ": 2^32 vertices or more").c_str());
 	MSH_HIP(m, hipSetDevice(m->device));
 	m->have_velocities = false;
 	const size_t nv = (size_t)m->n_vertices;
 	int rc = grow(m, &m->vvel, &m->vvcap, nv ? nv : 1, 24);
 	if (rc != LFA_OK) return rc;
-	if (!m->vel_out) MSH_HIP(m, hipMalloc(&m->vel_out, 4));
+	if (!m->vel_out) MSH_HIP(m, hipMalloc(&m->vel_out, 8));
 	for (hipEvent_t &e : m->vel_ev)
 		if (!e) MSH_HIP(m, hipEventCreate(&e));
 	MSH_HIP(m, hipStreamSynchronize(s->stream));
 	MSH_HIP(m, hipEventRecord(m->vel_ev[0], m->stream));
-	rc = lfa_sample_velocity_launch(s, m->stream, m->vpos, nv, m->vvel, nullptr, m->vel_out);
+	rc = lfa_sample_velocity_launch(s, m->stream, m->vpos, nv, rule, z_lo, z_hi, m->vvel, nullptr, m->vel_out);
 	if (rc != LFA_OK) return mfail(m, rc, lfa_last_error(s));
 	MSH_HIP(m, hipEventRecord(m->vel_ev[1], m->stream));
-	uint32_t count = 0;
-	MSH_HIP(m, hipMemcpyAsync(&count, m->vel_out, 4, hipMemcpyDeviceToHost, m->stream));
-	MSH_HIP(m, hipStreamSynchronize(m->stream));
+	uint32_t count[2] = {0, 0};
+	MSH_HIP(m, hipMemcpyAsync(count, m->vel_out, 8, hipMemcpyDeviceToHost, m->stream));
+	MSH_HIP(m, hipStreamSynchronize(m->stream));  // (the rules of a slab run sit in the simulation's io buffer: the kernel is done with them)
 	m->have_velocities = true;
-	if (n_outside) *n_outside = count;
+	counts[0] = count[0];
+	counts[1] = count[1];
 	return LFA_OK;
+}
+
+extern "C" int lfa_mesher_vertex_velocities(lfa_mesher *m, lfa_sim *s, uint64_t *n_outside) {
+	if (!m || !s) return LFA_E_INVALID;
+	uint64_t counts[2] = {0, 0};
+	const int rc = vertex_velocities(m, s, false, counts);
+	if (rc == LFA_OK && n_outside) *n_outside = counts[0];
+	return rc;
+}
+
+extern "C" int lfa_mesher_vertex_velocities_collective(lfa_mesher *m, lfa_sim *s, uint64_t counts[2]) {
+	if (!m || !s) return LFA_E_INVALID;
+	uint64_t c[2] = {0, 0};
+	const int rc = vertex_velocities(m, s, true, c);
+	if (counts) {
+		counts[0] = c[0];
+		counts[1] = c[1];
+	}
+	return rc;
 }
 
 extern "C" int lfa_mesher_download_velocities(lfa_mesher *m, double *velocity) {
