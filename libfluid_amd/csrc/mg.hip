@@ -72,6 +72,21 @@ struct lfa_mg_level {
 	unsigned long long *xq = nullptr;
 	int xq_sections = 0;  // 3: [x | b | y] (a level inside the launch), 1: x alone (the level fused in front of it)
 };
+/// The launch layout of a V-cycle. It follows from the levels' tile counts, the knobs, lfa_sim::co_disabled, the element type and
+/// the device share, all of which change only at a set-up (or when a handle retreats): mg_plan_t decides, mg_apply_t executes.
+struct MgPlan {
+	int last = 0;   // coarsest level that runs (0: the finest level's two sweeps alone)
+	int tail = 0;   // first level inside k_mg_coarse / k_mg_tail
+	int top = -1;   // level fused in front of / behind the resident workgroups of k_mg_coarse (-1: none; whole cycles only)
+	int D = 0;      // distributed levels (slabs)
+	bool persist = false;      // k_mg_coarse (false: a launch per phase and k_mg_tail)
+	bool tagged = false;       // ... with the tagged hand-off (co_put / co_get)
+	bool co_disabled = false;  // lfa_sim::co_disabled the plan was made for
+	struct Level {
+		bool cp = false;          // cell-parallel kernels (k_mg_*_cp) instead of a wave per tile
+		int g_down = 1, g_up = 1;  // workgroups of the level's launches on the way down / up
+	} lv[MG_MAX_LEVELS];
+};
 struct lfa_mg {
 	int n_levels = 0;
 	lfa_mg_level lv[MG_MAX_LEVELS];
@@ -104,6 +119,7 @@ struct lfa_mg {
 	unsigned solid_epoch = 0;     // solid mask the level-1 types were computed for
 	uint32_t *counts = nullptr;   // device, active tiles per level (single-domain set-up, read back once)
 	unsigned co_tag = 0;          // k_mg_coarse: launch counter = the value its ready flags are raised to (lfa_mg_level::ready)
+	MgPlan plan;                  // the V-cycle's launch layout for the last set-up
 	int launches_per_cycle = 0;   // launches of the last V-cycle incl. the AXPY / pre-smoothing kernel (lfa_get_solver_stats)
 	int first_co = 0;             // first level inside k_mg_coarse at the last V-cycle (0: launch-per-phase path)
 };
@@ -2239,8 +2255,8 @@ bool mg_dist(const lfa_sim *s) { return s->dist && (s->dist->nranks > 1 || s->kn
 }  // namespace
 
 // ================================================================================================= host side
-// Kernels whose workgroups wait for each other (k_mg_coarse) need all of them resident together; `fits` below sizes
-// one launch against the whole device. Independent handles on one GPU - several simulations of one host process, each on its own
+// Kernels whose workgroups wait for each other (k_mg_coarse) need all of them resident together; `fits` in mg_plan_t
+// sizes one launch against the whole device. Independent handles on one GPU - several simulations of one host process, each on its own
 // thread and stream, as the C ABI allows (include/libfluid_amd.h: "different handles are independent"; the Maya host holds one
 // fluid node per simulated object, plugins/maya/nodes/grid_node.cpp:256) - could have two such launches in flight, each with part
 // of its workgroups resident and waiting for the rest. While more than one handle is alive on a device every such launch
@@ -2290,29 +2306,42 @@ void lfa_co_gate_handle(int device, int delta) {
 	g.handles += delta;
 }
 
+/// Frees a level's device arrays and leaves it empty; the first error, if any.
+static hipError_t mg_free_level(lfa_mg_level &L) {
+	hipError_t rc = hipSuccess, e;
+	void *ptrs[] = {L.tiles, L.nbr, L.ctype, L.abits, L.x, L.b, L.y, L.flag, L.prev_flag, L.ready, L.xq};
+	for (void *p : ptrs)
+		if (p && (e = hipFree(p)) != hipSuccess && rc == hipSuccess) rc = e;
+	L = lfa_mg_level();
+	return rc;
+}
+
 void lfa_mg_free(lfa_sim *s) {
 	if (!s->mg) return;
-	for (auto &L : s->mg->lv) {
-		void *ptrs[] = {L.tiles, L.nbr, L.ctype, L.abits, L.x, L.b, L.y, L.flag, L.prev_flag, L.ready, L.xq};
-		for (void *p : ptrs)
-			if (p) (void)hipFree(p);
-	}
-	if (s->mg->l1_dirty) (void)hipFree(s->mg->l1_dirty);
-	if (s->mg->l1_has_fluid) (void)hipFree(s->mg->l1_has_fluid);
-	if (s->mg->slot0) (void)hipFree(s->mg->slot0);
-	if (s->mg->top_ring) (void)hipFree(s->mg->top_ring);
-	if (s->mg->top_buf) (void)hipFree(s->mg->top_buf);
-	if (s->mg->counts) (void)hipFree(s->mg->counts);
+	lfa_mg &M = *s->mg;
+	for (auto &L : M.lv) (void)mg_free_level(L);
+	void *ptrs[] = {M.l1_dirty, M.l1_has_fluid, M.slot0, M.top_ring, M.top_buf, M.counts};
+	for (void *p : ptrs)
+		if (p) (void)hipFree(p);
 	delete s->mg;
 	s->mg = nullptr;
 }
 
-/// Builds the hierarchy for the current unknown set (after lfa_build_rhs: A bytes and types of the step are on the device).
-template <typename real> static int mg_setup_t(lfa_sim *s) {
-	if (!s->mg) s->mg = new lfa_mg();
+// ------------------------------------------------------------------------------------------------ set-up, in stages
+/// What the stages of one set-up share.
+struct MgSetup {
+	std::vector<GridDims> gs;  // level grids
+	int D = 0;                 // distributed levels (0: single domain, >= 1: slabs)
+	bool realloc_all = false;  // stage 1 has allocated every array anew
+	bool same_tiles = false;   // the lists and tables on the device are still the right ones: no whole-array clears
+};
+
+/// Stage 1: level grids, the number of distributed levels and - when the hierarchy's shape or element type has changed - its arrays.
+template <typename real> static int mg_setup_levels(lfa_sim *s, MgSetup &U) {
 	lfa_mg &M = *s->mg;
 	// level grids: halve until one tile holds the whole level
-	std::vector<GridDims> gs{s->g};
+	std::vector<GridDims> &gs = U.gs;
+	gs.assign(1, s->g);
 	while ((gs.back().nx > 8 || gs.back().ny > 8 || gs.back().nz > 8) && (int)gs.size() < MG_MAX_LEVELS) {
 		GridDims c, f = gs.back();
 		c.nx = (f.nx + 1) / 2; c.ny = (f.ny + 1) / 2; c.nz = (f.nz + 1) / 2;
@@ -2323,18 +2352,13 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 	const int nl = (int)gs.size();
 	const bool dist = mg_dist(s);
 	const int d_max = s->knobs.mg_dist_levels > 0 ? std::min(s->knobs.mg_dist_levels, MG_DIST_MAX) : MG_DIST_MAX;
-	const int D = dist ? std::min({d_max, s->slab_align + 1, nl - 1}) : 0;
+	const int D = U.D = dist ? std::min({d_max, s->slab_align + 1, nl - 1}) : 0;
 	if (dist && D < 1) return lfa_fail(s, LFA_E_INVALID, "multigrid on slabs needs at least two levels");
-	const bool realloc_all = M.n_levels != nl || M.elem != sizeof(real) || M.n_dist != D ||
-	                         (nl > 1 && (M.lv[1].g.nx != gs[1].nx || M.lv[1].g.ny != gs[1].ny || M.lv[1].g.nz != gs[1].nz));
+	const bool realloc_all = U.realloc_all = M.n_levels != nl || M.elem != sizeof(real) || M.n_dist != D ||
+	                                         (nl > 1 && (M.lv[1].g.nx != gs[1].nx || M.lv[1].g.ny != gs[1].ny || M.lv[1].g.nz != gs[1].nz));
 	if (realloc_all) {
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		for (auto &L : M.lv) {
-			void *ptrs[] = {L.tiles, L.nbr, L.ctype, L.abits, L.x, L.b, L.y, L.flag, L.prev_flag, L.ready, L.xq};
-			for (void *p : ptrs)
-				if (p) LFA_HIP(s, hipFree(p));
-			L = lfa_mg_level();
-		}
+		for (auto &L : M.lv) LFA_HIP(s, mg_free_level(L));
 		M.n_levels = nl;
 		M.elem = sizeof(real);
 		M.n_dist = D;
@@ -2359,7 +2383,7 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 			L.g = gs[l];
 			L.ncp = (size_t)gs[l].nt * 512;
 			if (!dist) {
-				// single domain: tile lists and neighbour tables are built on the device (mg_device_lists); sized for every tile
+				// single domain: tile lists and neighbour tables are built on the device; sized for every tile
 				LFA_HIP(s, hipMalloc(&L.flag, (size_t)(gs[l].nt + 1) * 4));
 				LFA_HIP(s, hipMalloc(&L.prev_flag, (size_t)(gs[l].nt + 1) * 4));
 				LFA_HIP(s, hipMemsetAsync(L.prev_flag, 0, (size_t)(gs[l].nt + 1) * 4, s->stream));
@@ -2392,241 +2416,263 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 		M.lv[l].lo_layer = dist ? s->slab_lo >> l : 0;
 		M.lv[l].hi_layer = (!dist || s->slab_hi == s->g.ntz) ? gs[l].ntz : s->slab_hi >> l;
 	}
+	// closed tiles are solved on their own (k_mg_solve_closed): level 0 is what is left of the particle tiles. Never on slabs.
+	M.closed_out = nl > 1 && !s->dist && !s->knobs.mg_no_closed && s->tile_closed;
+	return LFA_OK;
+}
+
+/// Stage 2, single domain: flags -> scan -> compact per level on the device, ONE read-back of the counts, then the neighbour
+/// tables. (The host version - download of the particle tiles, sorted parent lists, binary-searched neighbours, an upload per
+/// level, what the slabs still do - cost 2.8 ms per step at C4 once the dam moves and the tile set changes every step.)
+template <typename real> static int mg_setup_device_lists(lfa_sim *s, MgSetup &U) {
+	lfa_mg &M = *s->mg;
+	const std::vector<GridDims> &gs = U.gs;
+	const int nl = M.n_levels;
+	const bool closed_out = M.closed_out;
+	// the levels from `small` on have at most MG_SMALL_NT tiles in their grid: their lists / tables come from three launches in all
+	int small = nl;
+	for (int l = nl - 1; l >= 1 && gs[l].nt <= MG_SMALL_NT; --l) small = l;
+	MgSmall SP;
+	SP.first = small;
+	SP.last = nl - 1;
+	for (int l = std::max(small - 1, 0); l < nl; ++l) {
+		const lfa_mg_level &L = M.lv[l];
+		SP.g[l] = gs[l];
+		SP.flag[l] = L.flag; SP.prev[l] = L.prev_flag; SP.tiles[l] = L.tiles; SP.nbr[l] = L.nbr;
+		SP.x[l] = L.x; SP.b[l] = L.b; SP.y[l] = L.y; SP.abits[l] = L.abits;
+	}
+	// level 1's types first: its active set is the parents of the particle tiles THAT HOLD AN UNKNOWN of level 1 (round 6)
+	const uint8_t *l1_has = (nl > 1 && !s->knobs.mg_no_prune) ? (const uint8_t *)M.l1_has_fluid : (const uint8_t *)nullptr;
+	if (nl > 1) {
+		hipLaunchKernelGGL(k_mg_types_from_fine_dirty, dim3(std::min(gs[1].nt, 8192)), dim3(256), 0, s->stream, gs[0], gs[1],
+		                   (const uint32_t *)s->tile_flag, (const uint32_t *)s->cell_count, (const uint8_t *)s->ctype,
+		                   (const uint8_t *)s->solid, M.lv[1].ctype, M.l1_dirty, M.solid_epoch != s->solid_epoch ? 1 : 0, M.l1_has_fluid);
+		M.solid_epoch = s->solid_epoch;
+	}
+	SP.l1_has_unknown = l1_has;
+	if (closed_out && !M.slot0) LFA_HIP(s, hipMalloc(&M.slot0, (size_t)gs[0].nt * 4));
+	hipLaunchKernelGGL(k_mg_flag_level0, dim3((gs[0].nt + 255) / 256), dim3(256), 0, s->stream, (const int *)s->tile_pslot,
+	                   closed_out ? (const uint8_t *)s->tile_closed : (const uint8_t *)nullptr, M.lv[0].flag, gs[0].nt);
+	for (int l = 1; l < small; ++l)
+		hipLaunchKernelGGL(k_mg_flag_parents, dim3((gs[l].nt + 255) / 256), dim3(256), 0, s->stream, gs[l - 1], gs[l],
+		                   (const uint32_t *)M.lv[l - 1].flag, M.lv[l].flag, l == 1 ? l1_has : (const uint8_t *)nullptr);
+	LFA_LAUNCH_CHECK(s);
+	for (int l = 0; l < small; ++l) {
+		lfa_mg_level &L = M.lv[l];
+		if (l == 0 && !closed_out) {  // the binning's own list
+			LFA_HIP(s, hipMemcpyAsync(L.tiles, s->ptiles, (size_t)s->n_ptiles * 4, hipMemcpyDeviceToDevice, s->stream));
+			continue;
+		}
+		LFA_TRY(lfa_exclusive_scan_u32(s, L.flag, s->tile_scan, (size_t)gs[l].nt, M.counts + l));  // (l >= 1: gs[l].nt <= nt / 8)
+		if (l == 0)
+			hipLaunchKernelGGL(k_mg_compact_slots, dim3((gs[0].nt + 255) / 256), dim3(256), 0, s->stream, (const uint32_t *)L.flag,
+			                   (const uint32_t *)s->tile_scan, L.tiles, M.slot0, gs[0].nt);
+		else
+			hipLaunchKernelGGL(k_mg_compact, dim3((gs[l].nt + 255) / 256), dim3(256), 0, s->stream, (const uint32_t *)L.flag,
+			                   (const uint32_t *)s->tile_scan, L.tiles, gs[l].nt);
+		LFA_LAUNCH_CHECK(s);
+	}
+	if (small < nl) {
+		hipLaunchKernelGGL(k_mg_small_lists, dim3(1), dim3(1024), 0, s->stream, SP, M.counts);
+		LFA_LAUNCH_CHECK(s);
+	}
+	uint32_t *hc = s->h_pinned + 64;
+	if (nl > 1) {
+		LFA_HIP(s, hipMemcpyAsync(hc, M.counts, (size_t)nl * 4, hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipStreamSynchronize(s->stream));
+	}
+	for (int l = small; l < nl; ++l) M.lv[l].n_tiles = (int)hc[l];
+	// (the children's set of the first small level: level small - 1 swaps its flag arrays in the loop below - after it the
+	// set of this set-up is its prev_flag; within the small levels the sets are the arrays k_mg_small_lists has just written)
+	for (int l = 0; l < small; ++l) {
+		lfa_mg_level &L = M.lv[l];
+		L.n_tiles = (l == 0 && !closed_out) ? s->n_ptiles : (int)hc[l];
+		if (L.n_tiles) {
+			hipLaunchKernelGGL(k_mg_build_nbr, dim3((L.n_tiles + 255) / 256), dim3(256), 0, s->stream, (const int *)L.tiles, L.n_tiles,
+			                   gs[l], (const uint32_t *)L.flag, L.nbr, gs[l > 0 ? l - 1 : 0],
+			                   l > 0 ? (const uint32_t *)M.lv[l - 1].prev_flag : (const uint32_t *)nullptr);  // (already swapped: the current set)
+			LFA_LAUNCH_CHECK(s);
+		}
+		if (l >= 1) {
+			hipLaunchKernelGGL(k_mg_clear_departed<real>, dim3(std::min(gs[l].nt, 4096)), dim3(256), 0, s->stream,
+			                   (const uint32_t *)L.prev_flag, (const uint32_t *)L.flag, gs[l].nt, (real *)L.x, (real *)L.b, (real *)L.y,
+			                   L.abits);
+			LFA_LAUNCH_CHECK(s);
+		}
+		std::swap(L.flag, L.prev_flag);  // prev_flag = this set-up's set; flag is rewritten by the next one
+	}
+	if (small < nl) {
+		SP.flag[small - 1] = M.lv[small - 1].prev_flag;  // (swapped just above: the current set of the level below)
+		hipLaunchKernelGGL(k_mg_small_tables<real>, dim3(16, nl - small), dim3(256), 0, s->stream, SP, (const uint32_t *)M.counts);
+		LFA_LAUNCH_CHECK(s);
+		for (int l = small; l < nl; ++l) std::swap(M.lv[l].flag, M.lv[l].prev_flag);
+	}
+	U.same_tiles = true;  // (k_mg_clear_departed has cleared what a departed tile left behind)
+	return LFA_OK;
+}
+
+/// Slabs: the first replicated level's active tiles `act` (all ranks') and their face neighbours - the tiles whose TYPES every rank
+/// needs (k_mg_abits looks one cell across a tile face; the coarser levels' types follow from these) - to host_ring / top_ring.
+static int mg_setup_ring(lfa_sim *s, const GridDims &g, const std::vector<int> &act) {
+	lfa_mg &M = *s->mg;
+	std::vector<int> ring;
+	ring.reserve(act.size() * 3);
+	for (int t : act) {
+		int tx, ty, tz;
+		tile_coords(g, t, tx, ty, tz);
+		ring.push_back(t);
+		if (tx > 0) ring.push_back(t - 1);
+		if (tx + 1 < g.ntx) ring.push_back(t + 1);
+		if (ty > 0) ring.push_back(t - g.ntx);
+		if (ty + 1 < g.nty) ring.push_back(t + g.ntx);
+		if (tz > 0) ring.push_back(t - g.ntx * g.nty);
+		if (tz + 1 < g.ntz) ring.push_back(t + g.ntx * g.nty);
+	}
+	std::sort(ring.begin(), ring.end());
+	ring.erase(std::unique(ring.begin(), ring.end()), ring.end());
+	if (ring == M.host_ring) return LFA_OK;
+	if (ring.size() > M.top_ring_cap) {
+		if (M.top_ring) LFA_HIP(s, hipFree(M.top_ring));
+		M.top_ring = nullptr;
+		M.top_ring_cap = ring.size() + ring.size() / 4 + 64;
+		LFA_HIP(s, hipMalloc(&M.top_ring, M.top_ring_cap * 4));
+	}
+	M.host_ring.swap(ring);  // (kept: the copy below reads it asynchronously)
+	if (!M.host_ring.empty())
+		LFA_HIP(s, hipMemcpyAsync(M.top_ring, M.host_ring.data(), M.host_ring.size() * 4, hipMemcpyHostToDevice, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	return LFA_OK;
+}
+
+/// Slabs: one level's list and neighbour table, from the sorted active tiles of the levels (`act`) to the device. `tiles`: the
+/// rank's particle tiles with the neighbours' of the adjacent layers.
+static int mg_setup_upload_level(lfa_sim *s, const MgSetup &U, int l, const std::vector<std::vector<int>> &act, const std::vector<int> &tiles) {
+	lfa_mg_level &L = s->mg->lv[l];
+	const std::vector<GridDims> &gs = U.gs;
+	const GridDims &g = gs[l];
+	const std::vector<int> &a = act[l];
+	L.n_tiles = (int)a.size();
+	if (a.size() > L.cap_tiles) {
+		if (L.tiles) LFA_HIP(s, hipFree(L.tiles));
+		if (L.nbr) LFA_HIP(s, hipFree(L.nbr));
+		L.tiles = L.nbr = nullptr;
+		L.cap_tiles = a.size() + a.size() / 4 + 16;
+		LFA_HIP(s, hipMalloc(&L.tiles, L.cap_tiles * 4));
+		LFA_HIP(s, hipMalloc(&L.nbr, L.cap_tiles * MG_NBR_STRIDE * 4));
+	}
+	if (a.empty()) return LFA_OK;
+	// neighbour tiles by binary search in the sorted list. Across a slab face of a distributed level the neighbour belongs
+	// to another rank: on the finest level it is active if it is one of that rank's particle tiles, on the others it always
+	// counts as active (its slice arrives with the layer exchange; an inactive tile holds zeros and no unknowns)
+	std::vector<int> nbr(a.size() * MG_NBR_STRIDE, 0);
+	const int sy = g.ntx, sz = g.ntx * g.nty;
+	for (size_t i = 0; i < a.size(); ++i) {
+		int tx, ty, tz;
+		tile_coords(g, a[i], tx, ty, tz);
+		const int cand[6] = {tx > 0 ? a[i] - 1 : -1,           tx + 1 < g.ntx ? a[i] + 1 : -1, ty > 0 ? a[i] - sy : -1,
+		                     ty + 1 < g.nty ? a[i] + sy : -1, tz > 0 ? a[i] - sz : -1,          tz + 1 < g.ntz ? a[i] + sz : -1};
+		for (int k = 0; k < 6; ++k) {
+			int v = -1;
+			const int nz = tz + (k == 4 ? -1 : (k == 5 ? 1 : 0));
+			if (cand[k] < 0) v = -1;
+			else if (l < U.D && (nz < L.lo_layer || nz >= L.hi_layer))
+				v = (l > 0 || std::binary_search(tiles.begin(), tiles.end(), cand[k])) ? cand[k] : -1;
+			else v = std::binary_search(a.begin(), a.end(), cand[k]) ? cand[k] : -1;
+			nbr[i * MG_NBR_STRIDE + k] = v;
+		}
+		nbr[i * MG_NBR_STRIDE + 6] = a[i];
+		int mask = 0;  // active child tiles (k_mg_coarse waits for their shares of this tile's right-hand side)
+		if (l > 0)
+			for (int k = 0; k < 8; ++k) {
+				const int cx = 2 * tx + (k & 1), cy = 2 * ty + ((k >> 1) & 1), cz = 2 * tz + (k >> 2);
+				if (cx < gs[l - 1].ntx && cy < gs[l - 1].nty && cz < gs[l - 1].ntz &&
+				    std::binary_search(act[l - 1].begin(), act[l - 1].end(), cx + gs[l - 1].ntx * (cy + gs[l - 1].nty * cz)))
+					mask |= 1 << k;
+			}
+		nbr[i * MG_NBR_STRIDE + 7] = mask;
+	}
+	LFA_HIP(s, hipMemcpyAsync(L.tiles, a.data(), a.size() * 4, hipMemcpyHostToDevice, s->stream));
+	LFA_HIP(s, hipMemcpyAsync(L.nbr, nbr.data(), nbr.size() * 4, hipMemcpyHostToDevice, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));  // the host vectors go out of scope
+	return LFA_OK;
+}
+
+/// Stage 3, slabs: active tiles per level on the host - a tile is active if one of its child tiles is; the first replicated
+/// level's are the union over the ranks (collective) - and, where they have changed, the lists and neighbour tables.
+static int mg_setup_host_lists(lfa_sim *s, MgSetup &U) {
+	lfa_mg &M = *s->mg;
+	const std::vector<GridDims> &gs = U.gs;
+	const int nl = M.n_levels, D = U.D;
+	const int n_all = s->n_ptiles_all;
+	std::vector<int> tiles(n_all);  // with the neighbours' particle tiles of the adjacent layers (ascending ids all the same)
+	LFA_HIP(s, hipMemcpyAsync(tiles.data(), s->ptiles_all, (size_t)n_all * 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	// The tile structure changes far less often than its contents: when the particle tiles are the ones of the last solve, the
+	// lists and neighbour tables on the device are kept (and no vector can hold values of a tile that has left the set).
+	bool same_tiles = !U.realloc_all && tiles == M.host_tiles;
+	std::vector<std::vector<int>> act(nl);
+	act[0].assign(tiles.begin() + s->p_off, tiles.begin() + s->p_off + s->n_ptiles);
+	for (int l = 1; l < nl; ++l) {
+		// active tiles of level l from those of level l - 1
+		const GridDims &f = gs[l - 1], &c = gs[l];
+		std::vector<int> &o = act[l];
+		o.reserve(act[l - 1].size() / 4 + 8);
+		for (int t : act[l - 1]) {
+			int tx, ty, tz;
+			tile_coords(f, t, tx, ty, tz);
+			o.push_back((tx >> 1) + c.ntx * ((ty >> 1) + c.nty * (tz >> 1)));
+		}
+		std::sort(o.begin(), o.end());
+		o.erase(std::unique(o.begin(), o.end()), o.end());
+		if (l != D) continue;
+		// the first replicated level: union of every rank's active tiles (one flag byte per tile, max all-reduce)
+		std::vector<uint8_t> flag((size_t)gs[l].nt, 0);
+		for (int t : act[l]) flag[t] = 1;
+		LFA_TRY(lfa_dist_ensure_xbuf(s, 0, flag.size()));
+		LFA_HIP(s, hipMemcpyAsync(s->xbuf[0], flag.data(), flag.size(), hipMemcpyHostToDevice, s->stream));
+		LFA_TRY(s->dist->allreduce_buf(s, s->xbuf[0], flag.size(), LFA_RED_U8, true));
+		LFA_HIP(s, hipMemcpyAsync(flag.data(), s->xbuf[0], flag.size(), hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipStreamSynchronize(s->stream));
+		act[l].clear();
+		for (int t = 0; t < gs[l].nt; ++t)
+			if (flag[t]) act[l].push_back(t);
+		same_tiles = same_tiles && act[l] == M.host_top;
+		if (M.top_packed) LFA_TRY(mg_setup_ring(s, gs[l], act[l]));
+	}
+	if (!same_tiles) {
+		for (int l = 0; l < nl; ++l) LFA_TRY(mg_setup_upload_level(s, U, l, act, tiles));
+		M.host_tiles = tiles;
+		M.host_top = act[D];
+	}
+	U.same_tiles = same_tiles;
+	return LFA_OK;
+}
+
+/// The first replicated level's packed buffer (slabs, LFA_MG_DIST_LEVELS) serves two uses: its ring tiles' types at the set-up and
+/// its active tiles' right-hand side in every V-cycle. Sized at the set-up for the larger, so that no V-cycle allocates.
+static int mg_setup_top_buf(lfa_sim *s, size_t need) {
+	lfa_mg &M = *s->mg;
+	if (need <= M.top_buf_cap) return LFA_OK;
+	if (M.top_buf) LFA_HIP(s, hipFree(M.top_buf));
+	M.top_buf = nullptr;
+	M.top_buf_cap = need + need / 4 + 4096;
+	LFA_HIP(s, hipMalloc(&M.top_buf, M.top_buf_cap));
+	return LFA_OK;
+}
+
+/// Stage 4: types and operators of the coarse levels (slabs: the first replicated level's types are combined across the ranks).
+template <typename real> static int mg_setup_operators(lfa_sim *s, const MgSetup &U) {
+	lfa_mg &M = *s->mg;
+	const std::vector<GridDims> &gs = U.gs;
+	const int nl = M.n_levels, D = U.D;
+	const bool dist = D > 0;
 	// the part of a level's arrays this rank touches: its own tile layers and one ghost layer per side (distributed levels)
 	auto layer_range = [&](int l, int &t0, int &t1) {
 		const lfa_mg_level &L = M.lv[l];
 		const int per = gs[l].ntx * gs[l].nty;
-		if (dist && l < D) {
-			t0 = std::max(L.lo_layer - 1, 0) * per;
-			t1 = std::min(L.hi_layer + 1, gs[l].ntz) * per;
-		} else {
-			t0 = 0;
-			t1 = gs[l].nt;
-		}
+		t0 = l < D ? std::max(L.lo_layer - 1, 0) * per : 0;
+		t1 = l < D ? std::min(L.hi_layer + 1, gs[l].ntz) * per : gs[l].nt;
 	};
-	bool same_tiles = false;
-	if (!dist) {
-		// ---- single domain: flags -> scan -> compact per level on the device, ONE read-back of the counts, then the neighbour
-		// tables. (The host version below - download of the particle tiles, sorted parent lists, binary-searched neighbours,
-		// an upload per level - cost 2.8 ms per step at C4 once the dam moves and the tile set changes every step.)
-		// the levels from `small` on have at most MG_SMALL_NT tiles in their grid: their lists / tables come from three launches in all
-		int small = nl;
-		for (int l = nl - 1; l >= 1 && gs[l].nt <= MG_SMALL_NT; --l) small = l;
-		MgSmall SP;
-		SP.first = small;
-		SP.last = nl - 1;
-		for (int l = std::max(small - 1, 0); l < nl; ++l) {
-			const lfa_mg_level &L = M.lv[l];
-			SP.g[l] = gs[l];
-			SP.flag[l] = L.flag; SP.prev[l] = L.prev_flag; SP.tiles[l] = L.tiles; SP.nbr[l] = L.nbr;
-			SP.x[l] = L.x; SP.b[l] = L.b; SP.y[l] = L.y; SP.abits[l] = L.abits;
-		}
-		// level 1's types first: its active set is the parents of the particle tiles THAT HOLD AN UNKNOWN of level 1 (round 6)
-		const uint8_t *l1_has = (nl > 1 && !s->knobs.mg_no_prune) ? (const uint8_t *)M.l1_has_fluid : (const uint8_t *)nullptr;
-		if (nl > 1) {
-			hipLaunchKernelGGL(k_mg_types_from_fine_dirty, dim3(std::min(gs[1].nt, 8192)), dim3(256), 0, s->stream, gs[0], gs[1],
-			                   (const uint32_t *)s->tile_flag, (const uint32_t *)s->cell_count, (const uint8_t *)s->ctype,
-			                   (const uint8_t *)s->solid, M.lv[1].ctype, M.l1_dirty, M.solid_epoch != s->solid_epoch ? 1 : 0, M.l1_has_fluid);
-			M.solid_epoch = s->solid_epoch;
-		}
-		SP.l1_has_unknown = l1_has;
-		// closed tiles are solved on their own (k_mg_solve_closed): level 0 is what is left of the particle tiles
-		const bool closed_out = nl > 1 && !s->dist && !s->knobs.mg_no_closed && s->tile_closed;
-		M.closed_out = closed_out;
-		if (closed_out && !M.slot0) LFA_HIP(s, hipMalloc(&M.slot0, (size_t)gs[0].nt * 4));
-		hipLaunchKernelGGL(k_mg_flag_level0, dim3((gs[0].nt + 255) / 256), dim3(256), 0, s->stream, (const int *)s->tile_pslot,
-		                   closed_out ? (const uint8_t *)s->tile_closed : (const uint8_t *)nullptr, M.lv[0].flag, gs[0].nt);
-		for (int l = 1; l < small; ++l)
-			hipLaunchKernelGGL(k_mg_flag_parents, dim3((gs[l].nt + 255) / 256), dim3(256), 0, s->stream, gs[l - 1], gs[l],
-			                   (const uint32_t *)M.lv[l - 1].flag, M.lv[l].flag, l == 1 ? l1_has : (const uint8_t *)nullptr);
-		LFA_LAUNCH_CHECK(s);
-		for (int l = 0; l < small; ++l) {
-			lfa_mg_level &L = M.lv[l];
-			if (l == 0 && !closed_out) {  // the binning's own list
-				LFA_HIP(s, hipMemcpyAsync(L.tiles, s->ptiles, (size_t)s->n_ptiles * 4, hipMemcpyDeviceToDevice, s->stream));
-				continue;
-			}
-			if (l == 0) {
-				LFA_TRY(lfa_exclusive_scan_u32(s, L.flag, s->tile_scan, (size_t)gs[0].nt, M.counts));
-				hipLaunchKernelGGL(k_mg_compact_slots, dim3((gs[0].nt + 255) / 256), dim3(256), 0, s->stream, (const uint32_t *)L.flag,
-				                   (const uint32_t *)s->tile_scan, L.tiles, M.slot0, gs[0].nt);
-				LFA_LAUNCH_CHECK(s);
-				continue;
-			}
-			LFA_TRY(lfa_exclusive_scan_u32(s, L.flag, s->tile_scan, (size_t)gs[l].nt, M.counts + l));  // gs[l].nt <= nt / 8
-			hipLaunchKernelGGL(k_mg_compact, dim3((gs[l].nt + 255) / 256), dim3(256), 0, s->stream, (const uint32_t *)L.flag,
-			                   (const uint32_t *)s->tile_scan, L.tiles, gs[l].nt);
-			LFA_LAUNCH_CHECK(s);
-		}
-		if (small < nl) {
-			hipLaunchKernelGGL(k_mg_small_lists, dim3(1), dim3(1024), 0, s->stream, SP, M.counts);
-			LFA_LAUNCH_CHECK(s);
-		}
-		uint32_t *hc = s->h_pinned + 64;
-		if (nl > 1) {
-			LFA_HIP(s, hipMemcpyAsync(hc, M.counts, (size_t)nl * 4, hipMemcpyDeviceToHost, s->stream));
-			LFA_HIP(s, hipStreamSynchronize(s->stream));
-		}
-		if (small < nl) {
-			// (the children's set of the first small level: level small - 1 swaps its flag arrays in the loop below - after it the
-			// set of this set-up is its prev_flag; within the small levels the sets are the arrays k_mg_small_lists has just written)
-			for (int l = small; l < nl; ++l) M.lv[l].n_tiles = (int)hc[l];
-		}
-		for (int l = 0; l < small; ++l) {
-			lfa_mg_level &L = M.lv[l];
-			L.n_tiles = (l == 0 && !closed_out) ? s->n_ptiles : (int)hc[l];
-			if (L.n_tiles) {
-				hipLaunchKernelGGL(k_mg_build_nbr, dim3((L.n_tiles + 255) / 256), dim3(256), 0, s->stream, (const int *)L.tiles, L.n_tiles,
-				                   gs[l], (const uint32_t *)L.flag, L.nbr, gs[l > 0 ? l - 1 : 0],
-				                   l > 0 ? (const uint32_t *)M.lv[l - 1].prev_flag : (const uint32_t *)nullptr);  // (already swapped: the current set)
-				LFA_LAUNCH_CHECK(s);
-			}
-			if (l >= 1) {
-				hipLaunchKernelGGL(k_mg_clear_departed<real>, dim3(std::min(gs[l].nt, 4096)), dim3(256), 0, s->stream,
-				                   (const uint32_t *)L.prev_flag, (const uint32_t *)L.flag, gs[l].nt, (real *)L.x, (real *)L.b, (real *)L.y,
-				                   L.abits);
-				LFA_LAUNCH_CHECK(s);
-			}
-			std::swap(L.flag, L.prev_flag);  // prev_flag = this set-up's set; flag is rewritten by the next one
-		}
-		if (small < nl) {
-			SP.flag[small - 1] = M.lv[small - 1].prev_flag;  // (swapped just above: the current set of the level below)
-			hipLaunchKernelGGL(k_mg_small_tables<real>, dim3(16, nl - small), dim3(256), 0, s->stream, SP, (const uint32_t *)M.counts);
-			LFA_LAUNCH_CHECK(s);
-			for (int l = small; l < nl; ++l) std::swap(M.lv[l].flag, M.lv[l].prev_flag);
-		}
-		same_tiles = true;  // nothing left for the host path / the whole-array clears below
-	}
-	// active tiles per level on the host: a tile is active if one of its child tiles is
-	if (dist) {
-		const int n_all = dist ? s->n_ptiles_all : s->n_ptiles;
-		std::vector<int> tiles(n_all);  // slabs: with the neighbours' particle tiles of the adjacent layers (ascending ids all the same)
-		LFA_HIP(s, hipMemcpyAsync(tiles.data(), dist ? s->ptiles_all : s->ptiles, (size_t)n_all * 4, hipMemcpyDeviceToHost, s->stream));
-		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		// The tile structure changes far less often than its contents: when the particle tiles are the ones of the last solve, the
-		// lists and neighbour tables on the device are kept (and no vector can hold values of a tile that has left the set).
-		same_tiles = !realloc_all && tiles == M.host_tiles;
-		std::vector<std::vector<int>> act(nl);
-		auto parents = [&](int l) {  // active tiles of level l from those of level l - 1
-			const GridDims &f = gs[l - 1], &c = gs[l];
-			std::vector<int> &o = act[l];
-			o.clear();
-			o.reserve(act[l - 1].size() / 4 + 8);
-			for (int t : act[l - 1]) {
-				int tx, ty, tz;
-				tile_coords(f, t, tx, ty, tz);
-				o.push_back((tx >> 1) + c.ntx * ((ty >> 1) + c.nty * (tz >> 1)));
-			}
-			std::sort(o.begin(), o.end());
-			o.erase(std::unique(o.begin(), o.end()), o.end());
-		};
-		if (dist || !same_tiles) {
-			if (dist) act[0].assign(tiles.begin() + s->p_off, tiles.begin() + s->p_off + s->n_ptiles);
-			else act[0] = tiles;
-			for (int l = 1; l < nl; ++l) {
-				parents(l);
-				if (dist && l == D) {
-					// the first replicated level: union of every rank's active tiles (one flag byte per tile, max all-reduce)
-					std::vector<uint8_t> flag((size_t)gs[l].nt, 0);
-					for (int t : act[l]) flag[t] = 1;
-					LFA_TRY(lfa_dist_ensure_xbuf(s, 0, flag.size()));
-					LFA_HIP(s, hipMemcpyAsync(s->xbuf[0], flag.data(), flag.size(), hipMemcpyHostToDevice, s->stream));
-					LFA_TRY(s->dist->allreduce_buf(s, s->xbuf[0], flag.size(), LFA_RED_U8, true));
-					LFA_HIP(s, hipMemcpyAsync(flag.data(), s->xbuf[0], flag.size(), hipMemcpyDeviceToHost, s->stream));
-					LFA_HIP(s, hipStreamSynchronize(s->stream));
-					act[l].clear();
-					for (int t = 0; t < gs[l].nt; ++t)
-						if (flag[t]) act[l].push_back(t);
-					same_tiles = same_tiles && act[l] == M.host_top;
-					if (M.top_packed) {
-						// the tiles whose TYPES every rank needs: the active ones and their face neighbours (k_mg_abits looks one cell
-						// across a tile face; the coarser levels' types follow from these)
-						std::vector<int> ring;
-						ring.reserve(act[l].size() * 3);
-						const GridDims &g = gs[l];
-						for (int t : act[l]) {
-							int tx, ty, tz;
-							tile_coords(g, t, tx, ty, tz);
-							ring.push_back(t);
-							if (tx > 0) ring.push_back(t - 1);
-							if (tx + 1 < g.ntx) ring.push_back(t + 1);
-							if (ty > 0) ring.push_back(t - g.ntx);
-							if (ty + 1 < g.nty) ring.push_back(t + g.ntx);
-							if (tz > 0) ring.push_back(t - g.ntx * g.nty);
-							if (tz + 1 < g.ntz) ring.push_back(t + g.ntx * g.nty);
-						}
-						std::sort(ring.begin(), ring.end());
-						ring.erase(std::unique(ring.begin(), ring.end()), ring.end());
-						if (ring != M.host_ring) {
-							if (ring.size() > M.top_ring_cap) {
-								if (M.top_ring) LFA_HIP(s, hipFree(M.top_ring));
-								M.top_ring = nullptr;
-								M.top_ring_cap = ring.size() + ring.size() / 4 + 64;
-								LFA_HIP(s, hipMalloc(&M.top_ring, M.top_ring_cap * 4));
-							}
-							M.host_ring.swap(ring);  // (kept: the copy below reads it asynchronously)
-							if (!M.host_ring.empty())
-								LFA_HIP(s, hipMemcpyAsync(M.top_ring, M.host_ring.data(), M.host_ring.size() * 4, hipMemcpyHostToDevice, s->stream));
-							LFA_HIP(s, hipStreamSynchronize(s->stream));
-						}
-					}
-				}
-			}
-		}
-		if (!same_tiles) {
-			for (int l = 0; l < nl; ++l) {
-				lfa_mg_level &L = M.lv[l];
-				const GridDims &g = gs[l];
-				const std::vector<int> &a = act[l];
-				L.n_tiles = (int)a.size();
-				if (a.size() > L.cap_tiles) {
-					if (L.tiles) LFA_HIP(s, hipFree(L.tiles));
-					if (L.nbr) LFA_HIP(s, hipFree(L.nbr));
-					L.tiles = L.nbr = nullptr;
-					L.cap_tiles = a.size() + a.size() / 4 + 16;
-					LFA_HIP(s, hipMalloc(&L.tiles, L.cap_tiles * 4));
-					LFA_HIP(s, hipMalloc(&L.nbr, L.cap_tiles * MG_NBR_STRIDE * 4));
-				}
-				if (a.empty()) continue;
-				// neighbour tiles by binary search in the sorted list. Across a slab face of a distributed level the neighbour belongs
-				// to another rank: on the finest level it is active if it is one of that rank's particle tiles, on the others it always
-				// counts as active (its slice arrives with the layer exchange; an inactive tile holds zeros and no unknowns)
-				std::vector<int> nbr(a.size() * MG_NBR_STRIDE, 0);
-				const int sy = g.ntx, sz = g.ntx * g.nty;
-				for (size_t i = 0; i < a.size(); ++i) {
-					int tx, ty, tz;
-					tile_coords(g, a[i], tx, ty, tz);
-					const int cand[6] = {tx > 0 ? a[i] - 1 : -1,           tx + 1 < g.ntx ? a[i] + 1 : -1, ty > 0 ? a[i] - sy : -1,
-					                     ty + 1 < g.nty ? a[i] + sy : -1, tz > 0 ? a[i] - sz : -1,          tz + 1 < g.ntz ? a[i] + sz : -1};
-					for (int k = 0; k < 6; ++k) {
-						int v = -1;
-						const int nz = tz + (k == 4 ? -1 : (k == 5 ? 1 : 0));
-						if (cand[k] < 0) v = -1;
-						else if (dist && l < D && (nz < L.lo_layer || nz >= L.hi_layer))
-							v = (l > 0 || std::binary_search(tiles.begin(), tiles.end(), cand[k])) ? cand[k] : -1;
-						else v = std::binary_search(a.begin(), a.end(), cand[k]) ? cand[k] : -1;
-						nbr[i * MG_NBR_STRIDE + k] = v;
-					}
-					nbr[i * MG_NBR_STRIDE + 6] = a[i];
-					int mask = 0;  // active child tiles (k_mg_coarse waits for their shares of this tile's right-hand side)
-					if (l > 0)
-						for (int k = 0; k < 8; ++k) {
-							const int cx = 2 * tx + (k & 1), cy = 2 * ty + ((k >> 1) & 1), cz = 2 * tz + (k >> 2);
-							if (cx < gs[l - 1].ntx && cy < gs[l - 1].nty && cz < gs[l - 1].ntz &&
-							    std::binary_search(act[l - 1].begin(), act[l - 1].end(), cx + gs[l - 1].ntx * (cy + gs[l - 1].nty * cz)))
-								mask |= 1 << k;
-						}
-					nbr[i * MG_NBR_STRIDE + 7] = mask;
-				}
-				LFA_HIP(s, hipMemcpyAsync(L.tiles, a.data(), a.size() * 4, hipMemcpyHostToDevice, s->stream));
-				LFA_HIP(s, hipMemcpyAsync(L.nbr, nbr.data(), nbr.size() * 4, hipMemcpyHostToDevice, s->stream));
-				LFA_HIP(s, hipStreamSynchronize(s->stream));  // the host vectors go out of scope
-			}
-			M.host_tiles = tiles;
-			if (dist) M.host_top = act[D];
-		}
-	}
-	// types and operators of the coarse levels
 	for (int l = 1; l < nl; ++l) {
 		lfa_mg_level &L = M.lv[l];
 		int t0, t1, zlo = 0, zhi = INT_MAX;
@@ -2645,7 +2691,7 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 		const size_t c0 = (size_t)t0 * 512, count = (size_t)(t1 - t0) * 512;
 		const unsigned grid = (unsigned)((count + 255) / 256);
 		if (l == 1 && !dist) {
-			// (done in front of the tile lists above)
+			// (done in front of the tile lists: mg_setup_device_lists)
 		} else if (l == 1)
 			hipLaunchKernelGGL(k_mg_types_from_fine, dim3(grid), dim3(256), 0, s->stream, gs[0], gs[1], c0, count, zlo, zhi,
 			                   (const uint32_t *)s->tile_flag, (const uint32_t *)s->cell_count, (const uint8_t *)s->ctype,
@@ -2658,13 +2704,7 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 			// packed: the ring tiles' types cross the ranks; every other tile of the level is a WALL on every rank - the same
 			// operator everywhere (a rank's own share alone would know more about its own layers than its peers do)
 			const int nr = (int)M.host_ring.size();
-			const size_t need = std::max((size_t)nr * 512, (size_t)1);
-			if (need > M.top_buf_cap) {
-				if (M.top_buf) LFA_HIP(s, hipFree(M.top_buf));
-				M.top_buf = nullptr;
-				M.top_buf_cap = need + need / 4 + 4096;
-				LFA_HIP(s, hipMalloc(&M.top_buf, M.top_buf_cap));
-			}
+			LFA_TRY(mg_setup_top_buf(s, std::max({(size_t)nr * 512, (size_t)L.n_tiles * 512 * sizeof(real), (size_t)1})));
 			if (nr) hipLaunchKernelGGL((k_mg_tiles_copy<uint8_t, true>), dim3(std::min(nr, 4096)), dim3(256), 0, s->stream, (const int *)M.top_ring, nr, L.ctype, (uint8_t *)M.top_buf);
 			LFA_HIP(s, hipMemsetAsync(L.ctype, MT_SOLID, L.ncp, s->stream));
 			LFA_TRY(s->dist->allreduce_buf(s, M.top_buf, (size_t)nr * 512, LFA_RED_U8, true));
@@ -2674,7 +2714,7 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 			LFA_TRY(s->dist->allreduce_buf(s, L.ctype, L.ncp, LFA_RED_U8, true));
 		// vectors of levels >= 1 are read where no tile of this solve writes (parents of ring cells): they must be zero there.
 		// Tiles of the current set are rewritten by every V-cycle, so clearing is only needed when the set has changed.
-		if (!same_tiles) {
+		if (!U.same_tiles) {
 			layer_range(l, t0, t1);
 			const size_t o = (size_t)t0 * 512, n = (size_t)(t1 - t0) * 512;
 			LFA_HIP(s, hipMemsetAsync((real *)L.x + o, 0, n * sizeof(real), s->stream));
@@ -2688,21 +2728,20 @@ template <typename real> static int mg_setup_t(lfa_sim *s) {
 			LFA_LAUNCH_CHECK(s);
 		}
 	}
-	// slabs: which cells across a slab face are unknowns (the up-sweep corrects ring values of unknowns only)
-	for (int l = 0; dist && l < D; ++l) {
+	return LFA_OK;
+}
+
+/// Stage 5, slabs: which cells across a slab face are unknowns (the up-sweep corrects ring values of unknowns only).
+static int mg_setup_exchange_abits(lfa_sim *s, const MgSetup &U) {
+	lfa_mg &M = *s->mg;
+	for (int l = 0; l < U.D; ++l) {
 		if (l == 0) LFA_TRY(lfa_dist_exchange_slices(s, s->abits, 1));
-		else LFA_TRY(lfa_dist_exchange_layer_slices(s, M.lv[l].abits, 1, gs[l].ntx * gs[l].nty, M.lv[l].lo_layer, M.lv[l].hi_layer));
+		else LFA_TRY(lfa_dist_exchange_layer_slices(s, M.lv[l].abits, 1, U.gs[l].ntx * U.gs[l].nty, M.lv[l].lo_layer, M.lv[l].hi_layer));
 	}
 	return LFA_OK;
 }
 
-int lfa_mg_setup(lfa_sim *s) {
-	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_setup_t<double>(s) : mg_setup_t<float>(s);
-}
-
-/// z = V(r) / scale and the partial sums of dot(z, r) (pcg_grid(n_ptiles) of them) into part_sigma.
-/// Level 0 uses the solver's own vectors: b = r (vr), pre-smoothed iterate in vq (free between the AXPYs and the next
-/// A s), result in vz. `level0_presmoothed`: vq already holds the pre-smoothed iterate (k_mg_axpy_presmooth).
+// ------------------------------------------------------------------------------------------------ the V-cycle's plan
 #define MG_TAIL_TILES 1  // levels with at most this many tiles run inside k_mg_tail: with the cell-parallel kernels for the small
                          // levels only the single-tile ones are worth keeping there (C2 / C4: 1.52 / 8.63 ms per step, 8: 1.55 / 8.69)
 #define MG_COARSEST_SWEEPS 2  // measured (moving dam, C2 / C3 / C4): 4: 14.0 / 15.05 / 16.15 iterations, 3: 14.05 / 15.0 / 16.0, 2: 14.1 / 15.05 / 15.85 - and 8 fewer half sweeps of latency per V-cycle
@@ -2717,25 +2756,248 @@ int lfa_mg_setup(lfa_sim *s) {
 #define MG_TOP_MAX_WGS 1024    // ... dealt to at most this many workgroups per phase
 #endif
 enum { MG_PART_PRE0 = 1, MG_PART_DOWN0 = 2, MG_PART_COARSE = 4, MG_PART_UP0 = 8, MG_PART_ALL = 15 };
-template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, bool level0_presmoothed, int parts = MG_PART_ALL) {
+
+/// How many workgroups of k_mg_coarse<real, ., tagged> with `nlev` levels inside the device holds at a time, by registers and LDS
+/// together (0 for an `nlev` outside 1 .. MG_CO_MAX_LEVELS). What the device queries return is kept, per device, for the life of the
+/// process: a process may hold handles on several GPUs and set them up from several threads. The first call for a device also
+/// raises the two kernels' dynamic LDS limit.
+template <typename real> static int mg_co_capacity(lfa_sim *s, bool tagged, int nlev, size_t *wgs) {
+	struct DevInfo {
+		int n_cu = 0;
+		bool attr_set = false;
+		int per_cu[2][MG_CO_MAX_LEVELS + 1];  // resident workgroups per CU by [tagged][levels inside], -1: not asked yet
+	};
+	static DevInfo info[64];
+	static std::mutex info_mutex;
+	std::lock_guard<std::mutex> lk(info_mutex);
+	DevInfo &d = info[s->device & 63];
+	*wgs = 0;
+	if (!d.n_cu) {
+		hipDeviceProp_t prop;
+		d.n_cu = (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+		for (auto &row : d.per_cu)
+			for (int &v : row) v = -1;
+	}
+	if (!d.attr_set) {
+		LFA_HIP(s, hipFuncSetAttribute((const void *)k_mg_coarse<real, MemAgent, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+		LFA_HIP(s, hipFuncSetAttribute((const void *)k_mg_coarse<real, MemAgent, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+		d.attr_set = true;
+	}
+	if (nlev < 1 || nlev > MG_CO_MAX_LEVELS) return LFA_OK;
+	int &per_cu = d.per_cu[tagged][nlev];
+	if (per_cu < 0) {
+		const size_t lds = (size_t)nlev * sizeof(CoLevel<real>) + 512 * sizeof(real) + 64;
+		const void *fn = tagged ? (const void *)k_mg_coarse<real, MemAgent, true> : (const void *)k_mg_coarse<real, MemAgent, false>;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess) {
+			(void)hipGetLastError();
+			per_cu = 0;
+		}
+	}
+	*wgs = (size_t)per_cu * (size_t)d.n_cu;
+	return LFA_OK;
+}
+
+/// The tagged words of a level (lfa_mg_level::xq) with at least `sections` sections; false: the level does without them.
+static bool mg_ensure_xq(lfa_sim *s, lfa_mg_level &L, int sections) {
+	if (L.xq && L.xq_sections >= sections) return true;
+	if (L.ncp > ((size_t)1 << 26)) return false;
+	if (L.xq) {
+		if (hipStreamSynchronize(s->stream) != hipSuccess || hipFree(L.xq) != hipSuccess) return false;
+		L.xq = nullptr;
+	}
+	if (hipMalloc(&L.xq, L.ncp * 8 * (size_t)sections) != hipSuccess) {
+		(void)hipGetLastError();
+		L.xq = nullptr;
+		L.xq_sections = 0;
+		return false;
+	}
+	L.xq_sections = sections;
+	return hipMemsetAsync(L.xq, 0, L.ncp * 8 * (size_t)sections, s->stream) == hipSuccess;  // (tag 0 is never used)
+}
+
+/// Stage 6 of the set-up (and again should a handle retreat without one): the launch layout of the V-cycles, lfa_mg::plan, from
+/// the levels' tile counts.
+template <typename real> static int mg_plan_t(lfa_sim *s) {
 	lfa_mg &M = *s->mg;
+	MgPlan &P = M.plan = MgPlan();
+	P.co_disabled = s->co_disabled;
 	const int nl = M.n_levels;
+	// cell-parallel kernels for levels of up to 1024 tiles (C4: levels 2 and 3; level 1 with 2048 tiles fills the chip with a
+	// wave per tile: 8.58 ms per step against 8.75 with cell-parallel kernels on every coarse level, 8.79 with none)
+	const int cp_max = 1024;
+	for (int l = 0; l < nl; ++l) {
+		const int n = M.lv[l].n_tiles;
+		MgPlan::Level &V = P.lv[l];
+		V.cp = l >= 1 && n <= cp_max;  // a workgroup per tile on the coarser levels (see k_mg_*_cp)
+		// wave per tile, down: no partial sums, no software pipeline (k_mg_residual_restrict: 63 VGPRs) - these kernels hide their
+		// loads with waves, not with the tuned 768-workgroup grid of the way up (mg_grid): MG_RR_GRID workgroups
+		V.g_down = std::max(1, std::min((n + PCG_WAVES - 1) / PCG_WAVES, MG_RR_GRID));
+		V.g_up = mg_grid(n);
+		if (V.cp) V.g_down = V.g_up = std::max(1, std::min(n, 8192));  // (a slab rank may hold no tile of a level)
+	}
 	// every level down to the single-tile one has active tiles - unless level 1 has none (nothing but spray: no coarse cell is an
 	// unknown), which leaves the finest level's sweeps alone
-	const int last = (nl > 1 && M.lv[1].n_tiles == 0 && !mg_dist(s)) ? 0 : nl - 1;
-	auto lvl = [&](int l) {
-		const lfa_mg_level &L = M.lv[l];
-		return MgLv<real>{L.tiles, L.nbr, L.n_tiles, L.g, l == 0 ? (const uint8_t *)s->abits : (const uint8_t *)L.abits,
-		                  l == 0 ? (real *)s->vr : (real *)L.b, l == 0 ? (real *)s->vq : (real *)L.x, l == 0 ? (real *)s->vz : (real *)L.y};
+	const int last = P.last = (nl > 1 && M.lv[1].n_tiles == 0 && !mg_dist(s)) ? 0 : nl - 1;
+	if (last == 0) return LFA_OK;
+	// slabs: levels < D run on the rank's own tiles with one slice per slab face exchanged where a stencil crosses it;
+	// levels >= D are replicated (identical work on every rank), so the tail workgroup may only hold replicated levels
+	const int D = P.D = mg_dist(s) ? M.n_dist : 0;
+	// Default: every level of at most MG_CO_MAX_TILES tiles (C4: levels >= 2, C2: levels >= 1) runs inside ONE launch, k_mg_coarse
+	// (phases chained by completion counters instead of kernel boundaries); the larger ones keep a launch per phase.
+	// LFA_MG_NO_PERSIST=1, and a handle that has given a device-side wait up (co_disabled): a launch per phase on every level.
+	P.persist = !s->knobs.mg_no_persist && !s->co_disabled;
+	if (!P.persist) {
+		int tail = last;  // first level handled by the single-workgroup tail
+		while (tail > 1 && M.lv[tail - 1].n_tiles <= MG_TAIL_TILES) --tail;
+		P.tail = std::max(tail, D);
+		return LFA_OK;
+	}
+	// every workgroup of k_mg_coarse must be resident at the same time (they wait for each other): one workgroup per tile of
+	// its first level, LDS per workgroup grows with the number of levels inside
+	size_t wgs;
+	LFA_TRY(mg_co_capacity<real>(s, false, 0, &wgs));  // (the LDS limit, whichever levels end up inside)
+	auto fits = [&](int first, bool tg) {
+		const int nlev = last - first + 1;
+		if (nlev > MG_CO_MAX_LEVELS || mg_co_capacity<real>(s, tg, nlev, &wgs) != LFA_OK) return false;
+		// ranks that share this GPU launch their k_mg_coarse at the same time: all of them must be resident together
+		const size_t share = s->dist ? (size_t)std::max(1, s->dist->device_share) : 1;
+		return M.lv[first].n_tiles <= MG_CO_MAX_TILES && (size_t)M.lv[first].n_tiles * share <= wgs;
 	};
+	auto first_inside = [&](bool tg) {
+		int tl = last;
+		while (tl > 1 && tl - 1 >= D && fits(tl - 1, tg)) --tl;
+		return std::max(tl, std::max(D, 1));
+	};
+	// the tagged hand-off inside the launch (co_put / co_get): fp32 vectors, and the exchange arrays of the levels inside allocated
+	bool tagged = sizeof(real) == 4 && !s->knobs.mg_no_tagged;
+	int tail = first_inside(tagged);
+	if (tagged) {
+		// 3 x 8 bytes per padded cell of every level inside (C4: level 2 is 128^3 cells = 50 MB); a level whose GRID is huge
+		// although few of its tiles are active (a small pool in a 2048^3 domain) keeps the flags instead
+		for (int l = tail; l <= last && tagged; ++l) tagged = mg_ensure_xq(s, M.lv[l], 3);
+		if (!tagged) tail = first_inside(false);
+	}
+	P.tail = tail;
+	P.tagged = tagged;
+	// the level above the first one inside joins the launch in launch order (k_mg_coarse: "fused in launch order"): never the
+	// finest level, never a distributed one, only the whole cycle (the bench entry points run parts of it)
+	// Up to MG_TOP_MAX_TILES tiles: measured (profiles/r05_top_ab.txt) C3 - level 1, ~600 tiles - 0.1223 -> 0.1150 ms per
+	// iteration; C4 - level 1, 2 400 tiles - 0.2610 -> 0.2658 and the overlapped step + 0.34 ms: 7 200 short workgroups have to be
+	// dispatched in front of / behind the resident ones, and the waiting ones hold slots the position correction wants.
+	// Not when slab ranks share this GPU (device_share > 1): launch order only holds inside ONE launch - another process's
+	// waiting phase-3 workgroups could hold the CU slots this launch's resident workgroups need (and the other way round),
+	// a cycle that would end at the 50 ms timeout and retire the kernel for good.
+	const bool shared_gpu = s->dist && s->dist->device_share > 1;
+	if (tagged && !shared_gpu && tail - 1 >= std::max(D, 1) && M.lv[tail - 1].n_tiles > 0 && !s->knobs.mg_no_top &&
+	    M.lv[tail - 1].n_tiles <= MG_TOP_MAX_TILES && mg_ensure_xq(s, M.lv[tail - 1], 1))
+		P.top = tail - 1;
+	return LFA_OK;
+}
+
+/// mg_plan_t for the handle's element type. Defined behind the V-cycle: the compiler emits the kernels in the order in which host
+/// code first names them, and k_mg_coarse, which the plan names first, keeps its place among the V-cycle's that way - the device
+/// code of this file can be compared byte for byte across changes of its host side.
+static int mg_plan(lfa_sim *s);
+
+/// Builds the hierarchy for the current unknown set (after lfa_build_rhs: A bytes and types of the step are on the device).
+template <typename real> static int mg_setup_t(lfa_sim *s) {
+	if (!s->mg) s->mg = new lfa_mg();
+	MgSetup U;
+	LFA_TRY(mg_setup_levels<real>(s, U));
+	if (U.D) LFA_TRY(mg_setup_host_lists(s, U));
+	else LFA_TRY(mg_setup_device_lists<real>(s, U));
+	LFA_TRY(mg_setup_operators<real>(s, U));
+	LFA_TRY(mg_setup_exchange_abits(s, U));
+	return mg_plan(s);
+}
+
+int lfa_mg_setup(lfa_sim *s) {
+	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_setup_t<double>(s) : mg_setup_t<float>(s);
+}
+
+// ------------------------------------------------------------------------------------------------ the V-cycle
+/// A level as the kernels see it. Level 0 uses the solver's own vectors: b = r (vr), pre-smoothed iterate in vq (free between the
+/// AXPYs and the next A s), result in vz.
+template <typename real> static MgLv<real> mg_lv(const lfa_sim *s, int l) {
+	const lfa_mg_level &L = s->mg->lv[l];
+	return MgLv<real>{L.tiles, L.nbr, L.n_tiles, L.g, l == 0 ? (const uint8_t *)s->abits : (const uint8_t *)L.abits,
+	                  l == 0 ? (real *)s->vr : (real *)L.b, l == 0 ? (real *)s->vq : (real *)L.x, l == 0 ? (real *)s->vz : (real *)L.y};
+}
+
+/// The levels from plan.tail on in one launch: k_mg_coarse in the form the plan has chosen (`co_kernel`; `top`: the level fused in
+/// front of and behind it, -1: none), or k_mg_tail on the launch-per-phase path.
+template <typename real> static int mg_launch_coarse(lfa_sim *s, int top, void (*co_kernel)(MgCo<real>, const int *)) {
+	lfa_mg &M = *s->mg;
+	const MgPlan &P = M.plan;
+	const int last = P.last, tail = P.tail;
+	const int *st = (const int *)s->pcg_state;
+	if (P.persist) {
+		MgCo<real> C;
+		C.first = tail;
+		C.last = last;
+		C.nsw = MG_COARSEST_SWEEPS;
+		C.inner = MG_INNER_SWEEPS;
+		for (int l = tail; l <= last; ++l) {
+			C.lv[l] = mg_lv<real>(s, l);
+			C.ready[l] = M.lv[l].ready;
+			C.xq[l] = P.tagged ? M.lv[l].xq : nullptr;
+			C.ncp[l] = M.lv[l].ncp;
+		}
+		if (M.co_tag >= 0x0FFFFFF0u) {  // (a flag holds tag << 4: after 2^28 launches the flags start over)
+			for (int l = 1; l <= last; ++l)
+				if (M.lv[l].ready) LFA_HIP(s, hipMemsetAsync(M.lv[l].ready, 0, (size_t)3 * M.lv[l].g.nt * sizeof(unsigned), s->stream));
+			M.co_tag = 0;
+		}
+		if (M.co_tag == 0)  // (first launch, or the tags start over: the tagged words too)
+			for (int l = 1; l <= last; ++l)
+				if (M.lv[l].xq) LFA_HIP(s, hipMemsetAsync(M.lv[l].xq, 0, M.lv[l].ncp * 8 * (size_t)M.lv[l].xq_sections, s->stream));
+		C.tag = ++M.co_tag;  // (0 is what the flags are initialised to)
+		C.top = top;
+		C.top_wgs = top >= 0 ? std::min(M.lv[top].n_tiles, MG_TOP_MAX_WGS) : 0;
+		if (top >= 0) {
+			C.lv[top] = mg_lv<real>(s, top);
+			C.xq[top] = M.lv[top].xq;
+			C.ncp[top] = M.lv[top].ncp;
+		}
+		C.abort = s->pcg_state + 2;
+		C.fault = s->knobs.mg_co_fault;
+		// one workgroup per tile of its first level: every workgroup owns one tile slot on every level it reaches
+		const int W = std::max(1, M.lv[tail].n_tiles) + 3 * C.top_wgs;
+		const size_t lds = std::max((size_t)(last - tail + 1) * sizeof(CoLevel<real>) + 512 * sizeof(real), sizeof(CpTile<real>) + 512 * sizeof(real));
+		CoGateScope gate(s);
+		// (dynamic LDS limit: mg_co_capacity)
+		hipLaunchKernelGGL(co_kernel, dim3(W), dim3(256), lds, s->stream, C, st);
+		if (gate.done() != LFA_OK) return lfa_fail(s, LFA_E_HIP, "chaining k_mg_coarse behind the device's previous one failed");
+	} else {
+		MgTail<real> T;
+		for (int l = tail; l <= last; ++l) T.lv[l] = mg_lv<real>(s, l);
+		T.first = tail;
+		T.last = last;
+		// the trailing run of single-tile levels (at most MG_CHAIN_MAX of them) stays inside one wave
+		T.chain = last;
+		while (T.chain > tail && last - (T.chain - 1) + 1 <= MG_CHAIN_MAX && M.lv[T.chain - 1].n_tiles == 1) --T.chain;
+		T.nsw = MG_COARSEST_SWEEPS;
+		T.inner = MG_INNER_SWEEPS;  // measured at C4: 19 iterations; 1 sweep on the tail levels: 22
+		hipLaunchKernelGGL(k_mg_tail<real>, dim3(1), dim3(MG_TAIL_WAVES * 64), 0, s->stream, T, st);
+	}
+	LFA_LAUNCH_CHECK(s);
+	return LFA_OK;
+}
+
+/// z = V(r) / scale and the partial sums of dot(z, r) (pcg_grid(n_ptiles) of them) into part_sigma.
+/// `level0_presmoothed`: vq already holds the pre-smoothed iterate (k_mg_axpy_presmooth).
+/// Executes lfa_mg::plan; `parts` other than MG_PART_ALL (lfa_mg_bench_part) run no level fused into k_mg_coarse's launch.
+template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, bool level0_presmoothed, int parts = MG_PART_ALL) {
+	lfa_mg &M = *s->mg;
+	const MgPlan &P = M.plan;
+	auto lvl = [&](int l) { return mg_lv<real>(s, l); };
 	const real inv_scale = (real)(1.0 / s->a_scale);
 	const int *st = (const int *)s->pcg_state;
-	if (last == 0) {  // a single level (a grid of one tile, or no coarse unknown anywhere): the two sweeps alone
+	if (P.last == 0) {  // a single level (a grid of one tile, or no coarse unknown anywhere): the two sweeps alone
 		const MgLv<real> L = lvl(0);
 		if (!level0_presmoothed && (parts & MG_PART_PRE0))
-			hipLaunchKernelGGL(k_mg_presmooth<real>, dim3(std::max(1, std::min((L.n_tiles + PCG_WAVES - 1) / PCG_WAVES, MG_RR_GRID))), dim3(256), 0,
-			                   s->stream, L, st);
-		if (parts & MG_PART_UP0) launch_up0<real>(mg_grid(L.n_tiles), s->stream, L, L.g, (const real *)nullptr, inv_scale, part_sigma, st);
+			hipLaunchKernelGGL(k_mg_presmooth<real>, dim3(P.lv[0].g_down), dim3(256), 0, s->stream, L, st);
+		if (parts & MG_PART_UP0) launch_up0<real>(P.lv[0].g_up, s->stream, L, L.g, (const real *)nullptr, inv_scale, part_sigma, st);
 		LFA_LAUNCH_CHECK(s);
 		if (parts == MG_PART_ALL) {
 			M.launches_per_cycle = 1 + 1;
@@ -2743,112 +3005,11 @@ template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, b
 		}
 		return LFA_OK;
 	}
-	int tail = last;  // first level handled by the single-workgroup tail
-	while (tail > 1 && M.lv[tail - 1].n_tiles <= MG_TAIL_TILES) --tail;
-	// slabs: levels < D run on the rank's own tiles with one slice per slab face exchanged where a stencil crosses it;
-	// levels >= D are replicated (identical work on every rank), so the tail workgroup may only hold replicated levels
-	const int D = mg_dist(s) ? M.n_dist : 0;
-	tail = std::max(tail, D);
-	// Default: every level of at most MG_CO_MAX_TILES tiles (C4: levels >= 2, C2: levels >= 1) runs inside ONE launch, k_mg_coarse
-	// (phases chained by completion counters instead of kernel boundaries); the larger ones keep a launch per phase.
-	// LFA_MG_NO_PERSIST=1, and a handle that has given a device-side wait up (co_disabled): a launch per phase on every level.
-	const bool persist = !s->knobs.mg_no_persist && !s->co_disabled;
-	// the tagged hand-off inside the launch (co_put / co_get): fp32 vectors, and the exchange arrays of the levels inside allocated
-	bool tagged = persist && sizeof(real) == 4 && !s->knobs.mg_no_tagged;
-	int top = -1;  // level fused in front of / behind the resident workgroups of k_mg_coarse
-	if (persist) {
-		// every workgroup of k_mg_coarse must be resident at the same time (they wait for each other): one workgroup per tile of
-		// its first level, LDS per workgroup grows with the number of levels inside
-		// (per device: a process may hold handles on several GPUs; what the queries return is kept - they sat in every V-cycle)
-		struct DevInfo {
-			int n_cu = 0;
-			bool attr_set = false;
-			int per_cu[2][MG_CO_MAX_LEVELS + 1];  // resident workgroups per CU by [tagged][levels inside], -1: not asked yet
-		};
-		static DevInfo info[64];
-		static std::mutex info_mutex;
-		DevInfo di;
-		const int dslot = s->device & 63;
-		{
-			std::lock_guard<std::mutex> lk(info_mutex);
-			DevInfo &d = info[dslot];
-			if (!d.n_cu) {
-				hipDeviceProp_t prop;
-				d.n_cu = (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-				for (auto &row : d.per_cu)
-					for (int &v : row) v = -1;
-			}
-			if (!d.attr_set) {
-				LFA_HIP(s, hipFuncSetAttribute((const void *)k_mg_coarse<real, MemAgent, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-				LFA_HIP(s, hipFuncSetAttribute((const void *)k_mg_coarse<real, MemAgent, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-				d.attr_set = true;
-			}
-			di = d;
-		}
-		const int n_cu = di.n_cu;
-		auto fits = [&](int first, bool tg) {
-			const int nlev = last - first + 1;
-			if (nlev > MG_CO_MAX_LEVELS) return false;
-			const size_t lds = (size_t)nlev * sizeof(CoLevel<real>) + 512 * sizeof(real) + 64;
-			int per_cu = di.per_cu[tg][nlev];  // by registers and LDS together
-			if (per_cu < 0) {
-				const void *fn = tg ? (const void *)k_mg_coarse<real, MemAgent, true> : (const void *)k_mg_coarse<real, MemAgent, false>;
-				if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess) {
-					(void)hipGetLastError();
-					per_cu = 0;
-				}
-				std::lock_guard<std::mutex> lk(info_mutex);
-				info[dslot].per_cu[tg][nlev] = di.per_cu[tg][nlev] = per_cu;
-			}
-			// ranks that share this GPU launch their k_mg_coarse at the same time: all of them must be resident together
-			const size_t share = s->dist ? (size_t)std::max(1, s->dist->device_share) : 1;
-			return M.lv[first].n_tiles <= MG_CO_MAX_TILES && (size_t)M.lv[first].n_tiles * share <= (size_t)per_cu * (size_t)n_cu;
-		};
-		auto plan = [&](bool tg) {
-			int tl = last;
-			while (tl > 1 && tl - 1 >= D && fits(tl - 1, tg)) --tl;
-			return std::max(tl, std::max(D, 1));
-		};
-		tail = plan(tagged);
-		auto ensure_xq = [&](int l, int sections) -> bool {
-			lfa_mg_level &L = M.lv[l];
-			if (L.xq && L.xq_sections >= sections) return true;
-			if (L.ncp > ((size_t)1 << 26)) return false;
-			if (L.xq) {
-				if (hipStreamSynchronize(s->stream) != hipSuccess || hipFree(L.xq) != hipSuccess) return false;
-				L.xq = nullptr;
-			}
-			if (hipMalloc(&L.xq, L.ncp * 8 * (size_t)sections) != hipSuccess) {
-				(void)hipGetLastError();
-				L.xq = nullptr;
-				L.xq_sections = 0;
-				return false;
-			}
-			L.xq_sections = sections;
-			return hipMemsetAsync(L.xq, 0, L.ncp * 8 * (size_t)sections, s->stream) == hipSuccess;  // (tag 0 is never used)
-		};
-		if (tagged) {
-			// 3 x 8 bytes per padded cell of every level inside (C4: level 2 is 128^3 cells = 50 MB); a level whose GRID is huge
-			// although few of its tiles are active (a small pool in a 2048^3 domain) keeps the flags instead
-			for (int l = tail; l <= last && tagged; ++l) tagged = ensure_xq(l, 3);
-			if (!tagged) tail = plan(false);
-		}
-		// the level above the first one inside joins the launch in launch order (k_mg_coarse: "fused in launch order"): never the
-		// finest level, never a distributed one, only the whole cycle (the bench entry points run parts of it)
-		// Up to MG_TOP_MAX_TILES tiles: measured (profiles/r05_top_ab.txt) C3 - level 1, ~600 tiles - 0.1223 -> 0.1150 ms per
-		// iteration; C4 - level 1, 2 400 tiles - 0.2610 -> 0.2658 and the overlapped step + 0.34 ms: 7 200 short workgroups have to be
-		// dispatched in front of / behind the resident ones, and the waiting ones hold slots the position correction wants.
-		// Not when slab ranks share this GPU (device_share > 1): launch order only holds inside ONE launch - another process's
-		// waiting phase-3 workgroups could hold the CU slots this launch's resident workgroups need (and the other way round),
-		// a cycle that would end at the 50 ms timeout and retire the kernel for good.
-		const bool shared_gpu = s->dist && s->dist->device_share > 1;
-		if (tagged && !shared_gpu && parts == MG_PART_ALL && tail - 1 >= std::max(D, 1) && M.lv[tail - 1].n_tiles > 0 && !s->knobs.mg_no_top &&
-		    M.lv[tail - 1].n_tiles <= MG_TOP_MAX_TILES && ensure_xq(tail - 1, 1))
-			top = tail - 1;
-	}
-	// cell-parallel kernels for levels of up to 1024 tiles (C4: levels 2 and 3; level 1 with 2048 tiles fills the chip with a
-	// wave per tile: 8.58 ms per step against 8.75 with cell-parallel kernels on every coarse level, 8.79 with none)
-	const int cp_max = 1024;
+	// Where the levels below the finest run depends on lfa_sim::co_disabled (the single level above does not). A handle that has
+	// retreated and got no set-up since - solve_t forces one, lfa_apply_preconditioner / lfa_bench_kernel do not - is planned anew.
+	if (P.co_disabled != s->co_disabled) LFA_TRY(mg_plan_t<real>(s));
+	const int tail = P.tail, D = P.D, top = parts == MG_PART_ALL ? P.top : -1;
+	void (*const co_kernel[2])(MgCo<real>, const int *) = {k_mg_coarse<real, MemAgent, false>, k_mg_coarse<real, MemAgent, true>};  // by [tagged] (named ahead of the loops' kernels: see mg_plan)
 	auto exchange_level = [&](int l, void *vec) -> int {
 		if (l == 0) return lfa_dist_exchange_slices(s, vec, (int)sizeof(real));
 		return lfa_dist_exchange_layer_slices(s, vec, (int)sizeof(real), M.lv[l].g.ntx * M.lv[l].g.nty, M.lv[l].lo_layer, M.lv[l].hi_layer);
@@ -2856,13 +3017,12 @@ template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, b
 	int launches = 0;
 	for (int l = 0; l < tail; ++l) {
 		const MgLv<real> L = lvl(l);
-		const int G = mg_grid(L.n_tiles);
-		const bool cp = l >= 1 && L.n_tiles <= cp_max;  // a workgroup per tile on the coarser levels (see k_mg_*_cp)
-		const int Gcp = std::max(1, std::min(L.n_tiles, 8192));  // (a slab rank may hold no tile of a level)
+		const bool cp = P.lv[l].cp;
+		const int G = P.lv[l].g_down;
 		if (l == top) continue;  // (inside k_mg_coarse)
 		if (!(l == 0 && level0_presmoothed) && (parts & (l == 0 ? MG_PART_PRE0 : MG_PART_COARSE))) {
-			if (cp) hipLaunchKernelGGL(k_mg_presmooth_cp<real>, dim3(Gcp), dim3(256), 0, s->stream, L, MG_INNER_SWEEPS, st);
-			else hipLaunchKernelGGL(k_mg_presmooth<real>, dim3(std::max(1, std::min((L.n_tiles + PCG_WAVES - 1) / PCG_WAVES, MG_RR_GRID))), dim3(256), 0, s->stream, L, st);  // (like the residual kernel: no partials, no pipeline)
+			if (cp) hipLaunchKernelGGL(k_mg_presmooth_cp<real>, dim3(G), dim3(256), 0, s->stream, L, MG_INNER_SWEEPS, st);
+			else hipLaunchKernelGGL(k_mg_presmooth<real>, dim3(G), dim3(256), 0, s->stream, L, st);
 			++launches;
 		}
 		if (l < D) {
@@ -2876,29 +3036,19 @@ template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, b
 				LFA_HIP(s, hipMemsetAsync(M.lv[D].b, 0, M.lv[D].ncp * sizeof(real), s->stream));
 		}
 		if (parts & (l == 0 ? MG_PART_DOWN0 : MG_PART_COARSE)) {
-			if (cp) hipLaunchKernelGGL(k_mg_residual_restrict_cp<real>, dim3(Gcp), dim3(256), 0, s->stream, L, M.lv[l + 1].g, (real *)M.lv[l + 1].b, st);
-			// (no partial sums, no software pipeline, 63 VGPRs: this kernel hides its loads with waves, not with the tuned 768-workgroup
-			// grid of its neighbours - MG_RR_GRID workgroups)
+			if (cp) hipLaunchKernelGGL(k_mg_residual_restrict_cp<real>, dim3(G), dim3(256), 0, s->stream, L, M.lv[l + 1].g, (real *)M.lv[l + 1].b, st);
 			else {
 				// (the finest level's launch also evaluates the stopping rule on the residual the AXPY kernel has just written)
 				MgStop stop{nullptr, 0, 0, 0.0, nullptr, nullptr};
 				if (l == 0 && level0_presmoothed && D == 0 && s->cur_iter >= 0 && s->cur_rmax_parts)
 					stop = MgStop{s->cur_rmax_parts, s->cur_rmax_n, s->cur_iter, s->prm.tolerance, s->pcg_state, s->pcg_hist};
-				hipLaunchKernelGGL(k_mg_residual_restrict<real>, dim3(std::max(1, std::min((L.n_tiles + PCG_WAVES - 1) / PCG_WAVES, MG_RR_GRID))), dim3(256), 0, s->stream, L, M.lv[l + 1].g, (real *)M.lv[l + 1].b, st, stop);
+				hipLaunchKernelGGL(k_mg_residual_restrict<real>, dim3(G), dim3(256), 0, s->stream, L, M.lv[l + 1].g, (real *)M.lv[l + 1].b, st, stop);
 			}
 			++launches;
 		}
 		LFA_LAUNCH_CHECK(s);
 		if (l < D && l + 1 == D && M.top_packed) {
-			const int nt = M.lv[D].n_tiles;
-			const size_t need = std::max((size_t)nt * 512 * sizeof(real), (size_t)1);
-			if (need > M.top_buf_cap) {
-				LFA_HIP(s, hipStreamSynchronize(s->stream));
-				if (M.top_buf) LFA_HIP(s, hipFree(M.top_buf));
-				M.top_buf = nullptr;
-				M.top_buf_cap = need + need / 4 + 4096;
-				LFA_HIP(s, hipMalloc(&M.top_buf, M.top_buf_cap));
-			}
+			const int nt = M.lv[D].n_tiles;  // (top_buf holds them: mg_setup_top_buf)
 			if (nt) hipLaunchKernelGGL((k_mg_tiles_copy<real, true>), dim3(std::min(nt, 4096)), dim3(256), 0, s->stream, (const int *)M.lv[D].tiles, nt, (real *)M.lv[D].b, (real *)M.top_buf);
 			LFA_TRY(s->dist->allreduce_buf(s, M.top_buf, (size_t)nt * 512, sizeof(real) == 4 ? LFA_RED_F32 : LFA_RED_F64, false));
 			if (nt) hipLaunchKernelGGL((k_mg_tiles_copy<real, false>), dim3(std::min(nt, 4096)), dim3(256), 0, s->stream, (const int *)M.lv[D].tiles, nt, (real *)M.lv[D].b, (real *)M.top_buf);
@@ -2906,69 +3056,19 @@ template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, b
 		} else if (l < D && l + 1 == D)
 			LFA_TRY(s->dist->allreduce_buf(s, M.lv[D].b, M.lv[D].ncp, sizeof(real) == 4 ? LFA_RED_F32 : LFA_RED_F64, false));
 	}
-	if ((parts & MG_PART_COARSE) && persist) {
-		MgCo<real> C;
-		for (int l = tail; l <= last; ++l) C.lv[l] = lvl(l);
-		C.first = tail;
-		C.last = last;
-		C.nsw = MG_COARSEST_SWEEPS;
-		C.inner = MG_INNER_SWEEPS;
-		for (int l = tail; l <= last; ++l) C.ready[l] = M.lv[l].ready;
-		if (M.co_tag >= 0x0FFFFFF0u) {  // (a flag holds tag << 4: after 2^28 launches the flags start over)
-			for (int l = 1; l <= last; ++l)
-				if (M.lv[l].ready) LFA_HIP(s, hipMemsetAsync(M.lv[l].ready, 0, (size_t)3 * M.lv[l].g.nt * sizeof(unsigned), s->stream));
-			M.co_tag = 0;
-		}
-		if (M.co_tag == 0)  // (first launch, or the tags start over: the tagged words too)
-			for (int l = 1; l <= last; ++l)
-				if (M.lv[l].xq) LFA_HIP(s, hipMemsetAsync(M.lv[l].xq, 0, M.lv[l].ncp * 8 * (size_t)M.lv[l].xq_sections, s->stream));
-		C.tag = ++M.co_tag;  // (0 is what the flags are initialised to)
-		for (int l = tail; l <= last; ++l) {
-			C.xq[l] = tagged ? M.lv[l].xq : nullptr;
-			C.ncp[l] = M.lv[l].ncp;
-		}
-		C.top = top;
-		C.top_wgs = top >= 0 ? std::min(M.lv[top].n_tiles, MG_TOP_MAX_WGS) : 0;
-		if (top >= 0) {
-			C.lv[top] = lvl(top);
-			C.xq[top] = M.lv[top].xq;
-			C.ncp[top] = M.lv[top].ncp;
-		}
-		C.abort = s->pcg_state + 2;
-		C.fault = s->knobs.mg_co_fault;
-		// one workgroup per tile of its first level: every workgroup owns one tile slot on every level it reaches
-		const int W = std::max(1, M.lv[tail].n_tiles) + 3 * C.top_wgs;
-		const size_t lds = std::max((size_t)(last - tail + 1) * sizeof(CoLevel<real>) + 512 * sizeof(real), sizeof(CpTile<real>) + 512 * sizeof(real));
-		CoGateScope gate(s);
-		// (dynamic LDS limit: set where `fits` is)
-		if (tagged) hipLaunchKernelGGL((k_mg_coarse<real, MemAgent, true>), dim3(W), dim3(256), lds, s->stream, C, st);
-		else hipLaunchKernelGGL((k_mg_coarse<real, MemAgent, false>), dim3(W), dim3(256), lds, s->stream, C, st);
-		if (gate.done() != LFA_OK) return lfa_fail(s, LFA_E_HIP, "chaining k_mg_coarse behind the device's previous one failed");
-		LFA_LAUNCH_CHECK(s);
-		++launches;
-	} else if (parts & MG_PART_COARSE) {
-		MgTail<real> T;
-		for (int l = tail; l <= last; ++l) T.lv[l] = lvl(l);
-		T.first = tail;
-		T.last = last;
-		// the trailing run of single-tile levels (at most MG_CHAIN_MAX of them) stays inside one wave
-		T.chain = last;
-		while (T.chain > tail && last - (T.chain - 1) + 1 <= MG_CHAIN_MAX && M.lv[T.chain - 1].n_tiles == 1) --T.chain;
-		T.nsw = MG_COARSEST_SWEEPS;
-		T.inner = MG_INNER_SWEEPS;  // measured at C4: 19 iterations; 1 sweep on the tail levels: 22
-		hipLaunchKernelGGL(k_mg_tail<real>, dim3(1), dim3(MG_TAIL_WAVES * 64), 0, s->stream, T, st);
-		LFA_LAUNCH_CHECK(s);
+	if (parts & MG_PART_COARSE) {
+		LFA_TRY(mg_launch_coarse<real>(s, top, co_kernel[P.tagged]));
 		++launches;
 	}
 	for (int l = tail - 1; l >= 0; --l) {
 		const MgLv<real> L = lvl(l);
-		const int G = mg_grid(L.n_tiles);
+		const int G = P.lv[l].g_up;
 		if (l == top) continue;  // (inside k_mg_coarse)
 		if (!(parts & (l == 0 ? MG_PART_UP0 : MG_PART_COARSE))) continue;
 		if (l == 0)
 			launch_up0<real>(G, s->stream, L, M.lv[1].g, (const real *)M.lv[1].y, inv_scale, part_sigma, st);
-		else if (L.n_tiles <= cp_max)
-			hipLaunchKernelGGL(k_mg_prolong_postsmooth_cp<real>, dim3(std::max(1, std::min(L.n_tiles, 8192))), dim3(256), 0, s->stream, L, M.lv[l + 1].g,
+		else if (P.lv[l].cp)
+			hipLaunchKernelGGL(k_mg_prolong_postsmooth_cp<real>, dim3(G), dim3(256), 0, s->stream, L, M.lv[l + 1].g,
 			                   (const real *)M.lv[l + 1].y, MG_INNER_SWEEPS, st);
 		else
 			hipLaunchKernelGGL((k_mg_prolong_postsmooth<real, false, 1>), dim3(G), dim3(256), 0, s->stream, L, M.lv[l + 1].g,
@@ -2980,7 +3080,7 @@ template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, b
 	}
 	if (parts == MG_PART_ALL) {
 		M.launches_per_cycle = launches + (level0_presmoothed ? 1 : 0);
-		M.first_co = persist ? (top >= 0 ? top : tail) : 0;
+		M.first_co = P.persist ? (top >= 0 ? top : tail) : 0;
 	}
 	return LFA_OK;
 }
@@ -2993,6 +3093,9 @@ void lfa_mg_stats(const lfa_sim *s, uint64_t *launches_per_cycle, uint64_t *leve
 
 int lfa_mg_apply(lfa_sim *s, double *part_sigma) {
 	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_apply_t<double>(s, part_sigma, false) : mg_apply_t<float>(s, part_sigma, false);
+}
+static int mg_plan(lfa_sim *s) {
+	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_plan_t<double>(s) : mg_plan_t<float>(s);
 }
 
 /// One PCG iteration's AXPYs + V-cycle: p += alpha s, r -= alpha q (alpha = sigma / (q.s) from the partials), signed max r

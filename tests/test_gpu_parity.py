@@ -479,14 +479,18 @@ def test_pcg_warm_start_converges_to_the_same_pressure_in_fewer_iterations():
 
 @pytest.mark.parametrize("dtype", [lfa.PCG_F32, lfa.PCG_F64])
 @pytest.mark.parametrize("size,block", [((136, 72, 104), ((0, 0, 0), (90, 50, 70))), ((64, 48, 40), ((3, 0, 2), (50, 30, 33))),
-                                        ((200, 120, 96), ((0, 0, 0), (200, 60, 96)))])
+                                        ((200, 120, 96), ((0, 0, 0), (200, 60, 96))), ((368, 16, 368), ((0, 0, 0), (368, 2, 368)))])
 def test_multigrid_single_launch_coarse_levels_are_bitwise_the_launch_per_phase_path(dtype, size, block, monkeypatch):
     """k_mg_coarse runs every phase of the coarse levels (pre-smoothing, residual + restriction, coarsest solve, prolongation +
     post-smoothing) inside one launch as dataflow between workgroups: one tile per workgroup and level, resident in LDS, ready
     flags tagged with the launch number, the level arrays accessed with agent-scope atomics. Same arithmetic per cell as the
     launch-per-phase kernels (LFA_MG_NO_PERSIST=1, the path a handle retreats to): identical iteration counts, bit-identical
-    pressures - on a ragged three-level grid, a small one (everything below the finest level inside the launch) and one whose
-    level 1 (375 tiles) is the launch's first level."""
+    pressures - on a ragged three-level grid, a small one (everything below the finest level inside the launch), one whose
+    level 1 (375 tiles) is the launch's first level, and a thin sheet whose level 1 is too large to be inside (more than 512
+    tiles) but small enough (at most 1024) to be fused in front of the launch, in launch order: the only grid here with such a
+    level. The sheet's active tiles per level are 2116, 529, 144, 36, 9, 4, 1 in every mode; with fp32 vectors the first level in
+    the launch is 1 by default and 2 with LFA_MG_NO_TOP=1 (5 and 8 launches per iteration; 20 with a launch per phase)."""
+    sheet = size == (368, 16, 368)
     res = []
     # "tagged": the default with fp32 vectors - values travel between the workgroups as {tag, value} words (fp64: the same as
     # "flags"); "flags": level arrays + ready flags (LFA_MG_NO_TAGGED=1); "phase": a launch per phase
@@ -509,6 +513,10 @@ def test_multigrid_single_launch_coarse_levels_are_bitwise_the_launch_per_phase_
             its.append(it)
         st = s.solver_stats()
         assert (st["mg_first_level_in_coarse_launch"] >= 1) == (mode != "phase") and st["device_waits_given_up"] == 0, st
+        if sheet:
+            assert list(s.mg_level_tiles()[:7]) == [2116, 529, 144, 36, 9, 4, 1]
+            if dtype == lfa.PCG_F32 and mode in ("tagged", "tagged-no-top"):
+                assert st["mg_first_level_in_coarse_launch"] == (1 if mode == "tagged" else 2), st
         res.append((its, s.pressure().copy()))
         s.close()
     for other in res[1:]:
