@@ -285,25 +285,38 @@ __device__ inline float hash_unit(uint32_t a, uint32_t b, uint32_t k) {
 // tile (one run), one cell of the x+1 tile, in that order = sorted by fine cell. The kernel itself stayed at 5.0 ms (PMC: 2.3e9
 // VALU wave-instructions, 70 % of them the pair walk, 47 of 64 lanes active on average - the lanes of a wave are particles of ~21
 // different fine cells whose runs have different lengths; staging 18 %, the per-particle epilogue 11 %).
-#define FT 11                                // fine cells per tile axis
-#define FT3 (FT * FT * FT)
+// Along x the fine cells are HALF as wide, 22 per tile of 8/22 = 0.3636 cells, and a particle walks the five around its own,
+// [hx - 2, hx + 2] = 1.82 cells (2 x 0.3636 = 0.7273 >= re, the same margin) instead of three whole ones = 2.18 cells: still nine
+// contiguous runs per particle, a sixth fewer candidates. y and z keep the whole fine cells - the runs stay as long as they are.
+// A block row is then 26 half cells - two of the x-1 tile, the own 22, two of the x+1 tile - which is the same particles as
+// before (two half cells are one fine cell exactly). Measured at C4: 2.10e9 -> 1.90e9 VALU wave-instructions, 4.57 -> 4.22 ms;
+// the index kernel, with twice the bins, 0.50 -> 0.54 ms (docs/experiments.md, "half-width fine cells along x").
+#define FT 11                                // fine cells per tile axis, y and z
+#define FTX (2 * FT)                         // fine (half) cells per tile along x
+#define FT3 (FTX * FT * FT)
 #define FT_STRIDE (FT3 + 1)                  // per tile: first record of every fine cell + the end
 #define FT_INV 1.375f                        // 11 / 8 (exact)
+#define FTX_INV 2.75f                        // 22 / 8 (exact)
 #define FT_PL ((FT + CORR_PARTS - 1) / CORR_PARTS)  // own fine layers (z) of a part (the last part takes what is left)
-#define FB 13                                // block: the own 11 x 11 fine cells + one on each side
+#define FB 13                                // block, y and z: the own 11 fine cells + one on each side
+#define FBX (FTX + 4)                        // block, x: the own 22 half cells + two on each side
 #define FBZ (FT_PL + 2)
-#define FB_N (FB * FB * FBZ)
+#define FB_N (FBX * FB * FBZ)
 #define FB_ROWS (FB * FBZ)
-#define FINE_CAP 5632                       // staged particles (13 x 13 x 8 fine cells hold 4160 at 8 per cell)
+#define FINE_CAP 5632                       // staged particles (13 x 13 x 8 whole fine cells hold 4160 at 8 per cell)
 #define FINE_CAP_BIG 12288                   // the second pass over flagged parts: 144 KB of positions, one workgroup per CU
-// (own particles the u16 list of k_correct_fine holds: twice its count array, where it lives; more are found through the row offsets)
+// (own particles the u16 list of k_correct_fine holds: its count array, where it lives; more are found through the row offsets)
 #define FIDX_THREADS 512   // (256: 0.75 ms at C4, 512: 0.58; FIDX_STAGE and FIDX_CNT are multiples of it)
-#define FIDX_CNT 1536                       // index kernel: >= FT3 + 1, a multiple of FIDX_THREADS
+#define FIDX_CNT (((FT3 + 1 + FIDX_THREADS - 1) / FIDX_THREADS) * FIDX_THREADS)  // index kernel: >= FT3 + 1, a multiple of FIDX_THREADS
 #define FIDX_STAGE 4608                      // records staged in LDS per tile by the index kernel (72 KB)
 
 __device__ inline int fine_coord(int l, float t) {
 	const int f = (int)(((float)l + t) * FT_INV);
 	return f < FT - 1 ? f : FT - 1;  // (t == 1 in the last cell: the max face belongs to the last fine cell)
+}
+__device__ inline int fine_coord_x(int l, float t) {
+	const int f = (int)(((float)l + t) * FTX_INV);
+	return f < FTX - 1 ? f : FTX - 1;
 }
 /// A record of the fine index: the in-cell fractions (exact) + the particle index, and the cell inside the tile in the two top
 /// bits of the fractions (a fraction is in [0, 1]: sign and top exponent bit are clear): lx whole (3 bits); of ly, lz the lowest
@@ -331,16 +344,23 @@ __device__ inline void fine_decode(const float4 &r, int fy, int fz, float t[3], 
 __global__ void __launch_bounds__(FIDX_THREADS)
 k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const float *t0, const float *t1, const float *t2,
                    const uint32_t *tile_start, const uint32_t *tile_count, uint32_t *fine_start, float4 *spos, uint32_t *key_copy) {
-	__shared__ uint32_t cnt[FIDX_CNT];
+	// Counters and cursors are relative to the tile's first record. A tile that fits the staging area has at most FIDX_STAGE < 2^16
+	// records: its counters are 16 bits wide, two per word (an atomic add on the word bumps one half; a cursor ends at the next
+	// cell's start, so the low half never carries into the high one) - the 2 663 of them take the room the 1 332 whole-cell words
+	// took, and the kernel stays at two workgroups per CU. A larger tile does not stage, so its counters - whole words, any
+	// count - live in the staging area.
+	__shared__ uint32_t cnt[FIDX_CNT / 2];
 	__shared__ uint32_t wsum[FIDX_THREADS / 64];
 	__shared__ float4 stage[FIDX_STAGE];
-	static_assert(FIDX_CNT % FIDX_THREADS == 0 && FIDX_STAGE % FIDX_THREADS == 0, "index kernel sizing");
+	static_assert(FIDX_CNT % (2 * FIDX_THREADS) == 0 && FIDX_STAGE % FIDX_THREADS == 0 && FIDX_STAGE < 65536 && FIDX_CNT <= 4 * FIDX_STAGE,
+	              "index kernel sizing");
 	constexpr int PER = FIDX_CNT / FIDX_THREADS;
+	uint32_t *cnt_big = (uint32_t *)stage;
 	auto fine_of = [&](uint32_t i, int l[3], float t[3]) -> int {
 		const uint32_t k = key[i];
 		l[0] = (int)(k & 7); l[1] = (int)((k >> 3) & 7); l[2] = (int)((k >> 6) & 7);
 		t[0] = t0[i]; t[1] = t1[i]; t[2] = t2[i];
-		return fine_coord(l[0], t[0]) + FT * (fine_coord(l[1], t[1]) + FT * fine_coord(l[2], t[2]));
+		return fine_coord_x(l[0], t[0]) + FTX * (fine_coord(l[1], t[1]) + FT * fine_coord(l[2], t[2]));
 	};
 	constexpr int RPT = FIDX_STAGE / FIDX_THREADS;  // particles per thread of a tile that fits the staging area: kept in registers
 	for (int slot = blockIdx.x; slot < n_ptiles; slot += gridDim.x) {
@@ -348,8 +368,13 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 		// ghost tiles (slab decomposition) keep their particles behind the live ones: the range end comes from the count
 		const uint32_t b = tile_start[tile], e = b + tile_count[tile];
 		const bool staged = e - b <= FIDX_STAGE;  // (uniform)
+		if (staged) {
 #pragma unroll
-		for (int k = 0; k < PER; ++k) cnt[threadIdx.x + FIDX_THREADS * k] = 0;
+			for (int k = 0; k < PER / 2; ++k) cnt[threadIdx.x + FIDX_THREADS * k] = 0;
+		} else {
+#pragma unroll
+			for (int k = 0; k < PER; ++k) cnt_big[threadIdx.x + FIDX_THREADS * k] = 0;
+		}
 		__syncthreads();
 		// pass 1: histogram. A tile that fits keeps what it has read - (fine cell << 9 | cell in the tile) and the fractions -
 		// in registers for pass 2 (reading key and t a second time was a third of the kernel's HBM traffic)
@@ -366,14 +391,14 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 					const int f = fine_of(i, l, t);
 					rf[r] = ((uint32_t)f << 9) | (uint32_t)(l[0] | (l[1] << 3) | (l[2] << 6));
 					r0[r] = t[0]; r1[r] = t[1]; r2[r] = t[2];
-					atomicAdd(&cnt[f], 1u);
+					atomicAdd(&cnt[f >> 1], 1u << (16 * (f & 1)));
 				}
 			}
 		} else {
 			for (uint32_t i = b + threadIdx.x; i < e; i += FIDX_THREADS) {
 				int l[3];
 				float t[3];
-				atomicAdd(&cnt[fine_of(i, l, t)], 1u);
+				atomicAdd(&cnt_big[fine_of(i, l, t)], 1u);
 			}
 		}
 		__syncthreads();
@@ -381,7 +406,7 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 		uint32_t c[PER], incl = 0;
 #pragma unroll
 		for (int k = 0; k < PER; ++k) {
-			c[k] = cnt[PER * threadIdx.x + k];
+			c[k] = staged ? (cnt[(PER / 2) * threadIdx.x + k / 2] >> (16 * (k & 1))) & 0xFFFFu : cnt_big[PER * threadIdx.x + k];
 			incl += c[k];
 		}
 		const uint32_t sum = incl;
@@ -393,14 +418,16 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 		}
 		if (lane == 63) wsum[wid] = incl;
 		__syncthreads();
-		uint32_t ex = b + incl - sum;
+		uint32_t ex = incl - sum;
 		for (int w = 0; w < wid; ++w) ex += wsum[w];
 		__syncthreads();
 #pragma unroll
 		for (int k = 0; k < PER; ++k) {
 			const int f = PER * threadIdx.x + k;
-			cnt[f] = ex;  // cursor
-			if (f <= FT3) fine_start[(size_t)tile * FT_STRIDE + f] = ex;
+			// cursor
+			if (!staged) cnt_big[f] = ex;
+			else if (k & 1) cnt[f >> 1] = (ex - c[k - (k & 1)]) | (ex << 16);
+			if (!staged && f <= FT3) fine_start[(size_t)tile * FT_STRIDE + f] = b + ex;  // (a staged tile: after pass 2)
 			ex += c[k];
 		}
 		__syncthreads();
@@ -410,9 +437,10 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 #pragma unroll
 			for (int r = 0; r < RPT; ++r)
 				if (rf[r] != 0xFFFFFFFFu) {
-					const uint32_t at = atomicAdd(&cnt[rf[r] >> 9], 1u);
-					stage[at - b] = fine_record((int)(rf[r] & 7), (int)((rf[r] >> 3) & 7), (int)((rf[r] >> 6) & 7), r0[r], r1[r], r2[r],
-					                            b + threadIdx.x + FIDX_THREADS * r);
+					const uint32_t f = rf[r] >> 9;
+					const uint32_t at = (atomicAdd(&cnt[f >> 1], 1u << (16 * (f & 1))) >> (16 * (f & 1))) & 0xFFFFu;
+					stage[at] = fine_record((int)(rf[r] & 7), (int)((rf[r] >> 3) & 7), (int)((rf[r] >> 6) & 7), r0[r], r1[r], r2[r],
+					                        b + threadIdx.x + FIDX_THREADS * r);
 				}
 			// `key_copy`: the keys of before the correction, for its fallback pass and lfa_correct_collide_undo - written here, from
 			// registers and together with the other stores (a store between the loads of pass 1 held them up: vmcnt is one
@@ -423,13 +451,17 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 					if (rf[r] != 0xFFFFFFFFu) key_copy[b + threadIdx.x + FIDX_THREADS * r] = ((uint32_t)tile << 9) | (rf[r] & 511u);
 			}
 			__syncthreads();
+			// the cells' first records: pass 2 has left the cursor of cell f - 1 at the start of cell f - consecutive threads write
+			// consecutive entries (from the scan, a thread's PER entries apiece, the stores were PER words apart)
+			for (int f = threadIdx.x; f <= FT3; f += FIDX_THREADS)
+				fine_start[(size_t)tile * FT_STRIDE + f] = b + (f ? (cnt[(f - 1) >> 1] >> (16 * ((f - 1) & 1))) & 0xFFFFu : 0u);
 			for (uint32_t k = threadIdx.x; k < e - b; k += FIDX_THREADS) spos[b + k] = stage[k];
 		} else {
 			for (uint32_t i = b + threadIdx.x; i < e; i += FIDX_THREADS) {
 				int l[3];
 				float t[3];
-				const uint32_t at = atomicAdd(&cnt[fine_of(i, l, t)], 1u);
-				spos[at] = fine_record(l[0], l[1], l[2], t[0], t[1], t[2], i);
+				const uint32_t at = atomicAdd(&cnt_big[fine_of(i, l, t)], 1u);
+				spos[b + at] = fine_record(l[0], l[1], l[2], t[0], t[1], t[2], i);
 				if (key_copy) key_copy[i] = key[i];
 			}
 		}
@@ -437,12 +469,12 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 	}
 }
 
-/// Where block fine cell (gx, gy, gz) - own-tile fine coordinates, -1 .. FT - lives: the source tile (-1: none) and its fine
-/// coordinates there.
+/// Where block fine cell (gx, gy, gz) - own-tile fine coordinates, -2 .. FTX + 1 in x, -1 .. FT in y and z - lives: the source tile
+/// (-1: none) and its fine coordinates there.
 __device__ inline int fine_source(const GridDims &g, const uint32_t *tile_count, int tx, int ty, int tz, int gx, int gy, int gz, int &fx,
                                   int &fy, int &fz) {
-	const int dx = gx < 0 ? -1 : (gx >= FT ? 1 : 0), dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0), dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
-	fx = gx - FT * dx; fy = gy - FT * dy; fz = gz - FT * dz;
+	const int dx = gx < 0 ? -1 : (gx >= FTX ? 1 : 0), dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0), dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
+	fx = gx - FTX * dx; fy = gy - FT * dy; fz = gz - FT * dz;
 	const int x = tx + dx, y = ty + dy, z = tz + dz;
 	if ((unsigned)x >= (unsigned)g.ntx || (unsigned)y >= (unsigned)g.nty || (unsigned)z >= (unsigned)g.ntz) return -1;
 	const int tile = x + g.ntx * (y + g.nty * z);
@@ -462,7 +494,7 @@ __device__ inline void correct_collide_record(size_t rk, const ParticleSoA &p, u
 	const int l[3] = {(int)(key_i & 7), (int)((key_i >> 3) & 7), (int)((key_i >> 6) & 7)};
 	const float t[3] = {__uint_as_float(__float_as_uint(me.x) & 0x3FFFFFFFu), __uint_as_float(__float_as_uint(me.y) & 0x3FFFFFFFu),
 	                    __uint_as_float(__float_as_uint(me.z) & 0x3FFFFFFFu)};
-	const int f[3] = {fine_coord(l[0], t[0]), fine_coord(l[1], t[1]), fine_coord(l[2], t[2])};
+	const int f[3] = {fine_coord_x(l[0], t[0]), fine_coord(l[1], t[1]), fine_coord(l[2], t[2])};
 	if (only_flagged) {
 		const int work = CORR_PARTS * (tile_pslot[tile] - p_off) + f[2] / FT_PL;
 		if (!((only_flagged[1 + (work >> 5)] >> (work & 31)) & 1u)) return;
@@ -474,11 +506,11 @@ __device__ inline void correct_collide_record(size_t rk, const ParticleSoA &p, u
 	double spring[3] = {0.0, 0.0, 0.0};
 	for (int dz = -1; dz <= 1; ++dz)
 		for (int dy = -1; dy <= 1; ++dy)
-			for (int dx = -1; dx <= 1; ++dx) {
+			for (int dx = -2; dx <= 2; ++dx) {  // (the five half cells of the tiled kernel's x-run, one at a time)
 				int sf[3];
 				const int src = fine_source(g, tile_count, tx, ty, tz, f[0] + dx, f[1] + dy, f[2] + dz, sf[0], sf[1], sf[2]);
 				if (src < 0) continue;
-				const uint32_t *fs = fine_start + (size_t)src * FT_STRIDE + (sf[0] + FT * (sf[1] + FT * sf[2]));
+				const uint32_t *fs = fine_start + (size_t)src * FT_STRIDE + (sf[0] + FTX * (sf[1] + FT * sf[2]));
 				const uint32_t kb = fs[0], ke = fs[1];
 				int stx, sty, stz;
 				tile_coords(g, src, stx, sty, stz);
@@ -541,7 +573,8 @@ k_correct_collide(size_t n, ParticleSoA p, uint32_t *out_key, float *out_tx, flo
 }
 
 /// LDS-tiled _correct_positions + _detect_collisions on the fine index. One workgroup per (particle tile, z part): part 0 moves the
-/// particles of FT_PL fine layers (the last part of what is left); the block staged in LDS is those layers + one fine cell all around.
+/// particles of FT_PL fine layers (the last part of what is left); the block staged in LDS is those layers + one fine cell all around
+/// (along x: two half cells).
 /// CAP: staged particles. <FINE_CAP, false> is the pass over every part (two workgroups per CU); <FINE_CAP_BIG, true> takes the parts
 /// the first pass has flagged in `only` (word 0: how many; a crowded neighbourhood late in a run) with the whole LDS of a CU to
 /// itself, and flags what does not fit even that for the global-gather kernel.
@@ -568,22 +601,26 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
                 const uint8_t *solid, const uint32_t *tile_count, const uint32_t *fine_start, const float4 *spos, MoveParams mp,
                 uint32_t *overflow_tiles, const uint8_t *tile_clear, const uint32_t *only) {
 	constexpr int T = ONLY ? CORR_THREADS_BIG : CORR_THREADS;  // threads of the workgroup
-	constexpr int CNT = ((FB_N + 1 + T - 1) / T) * T;        // >= FB_N + 1, a multiple of T
+	constexpr int CNT0 = ((FB_N + 1 + 2 * T - 1) / (2 * T)) * (2 * T);  // >= FB_N + 1, a multiple of 2 T
+	constexpr int CNT = ONLY && CNT0 < 4096 ? 4096 : CNT0;  // (the second pass has the room to list 4 096 own particles)
 	__shared__ float px[CAP], py[CAP], pz[CAP];
-	__shared__ uint32_t fcnt[CNT];          // particles per block fine cell; afterwards the own list (u16)
+	__shared__ uint32_t fcnt2[CNT / 2];     // particles per block fine cell (<= CAP), two cells per word; afterwards the own list
+	uint16_t *fcnt = (uint16_t *)fcnt2;
 	__shared__ uint16_t foff[FB_N + 1];        // first staged slot of every block fine cell
-	// Per fine row of the block, everything the staging derives from the row alone (8 words, read as two 128-bit halves):
+	// Per fine row of the block, everything the staging derives from the row alone: four words read as one 128-bit load,
 	// [0..2] source record of staged slot s in the row's three runs (x-1 tile, own x tile, x+1 tile) is base[seg] + s
 	// [3]    first slot of the own x run | first slot of the x+1 run << 16
-	// [4..5] 8 dy, 8 dz: the source tile's offset in cells     [6] y0 | z0 << 8: first cell of the fine row (fine_decode)
-	// [7]    own list: a slot s of the own x run is entry [7] + s; ROW_NOT_OWN: the row is not listed
-	__shared__ __attribute__((aligned(16))) uint32_t rowd[FB_ROWS * 8];
-	constexpr uint32_t ROW_NOT_OWN = 0x80000000u;  // (a listed base is within +- CAP)
+	// and one packed word (the half cells doubled count and offset arrays: the descriptors gave the LDS back),
+	// bits 0-2, 3-5  y0, z0: first cell of the fine row (fine_decode)     bits 6-10, 11-15  8 (dy + 1), 8 (dz + 1): the source
+	// tile's offset in cells     bits 16-31  own list: a slot s of the own x run is entry (signed) + s; ROW_NOT_OWN: not listed
+	__shared__ __attribute__((aligned(16))) uint32_t rowd[FB_ROWS * 4];
+	__shared__ uint32_t rowe[FB_ROWS];
+	constexpr int ROW_NOT_OWN = -32768;  // (a listed base is within -CAP .. CNT: 16 bits, signed)
 	__shared__ uint32_t ownoff[FT * FT_PL + 1];
 	__shared__ int srct[27];                   // the source tiles around the own one
 	__shared__ uint32_t wsum[T / 64];
-	uint16_t *own = (uint16_t *)fcnt;
-	static_assert(CNT > FB_N && CNT % T == 0, "fcnt sizing");
+	uint16_t *own = fcnt;
+	static_assert(CNT > FB_N && CNT % (2 * T) == 0 && FBX % 2 == 0 && CAP < 32768 && CNT < 32768, "fcnt sizing");
 	constexpr int PER = CNT / T;
 	const int nn[3] = {g.nx, g.ny, g.nz};
 	const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -619,29 +656,36 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 		asm volatile("" : "+v"(tid));
 		if (tid < 27) {
 			int fx, fy, fz;
-			srct[tid] = fine_source(g, tile_count, tx, ty, tz, FT * ((int)tid % 3 - 1), FT * (((int)tid / 3) % 3 - 1), FT * ((int)tid / 9 - 1), fx,
+			srct[tid] = fine_source(g, tile_count, tx, ty, tz, FTX * ((int)tid % 3 - 1), FT * (((int)tid / 3) % 3 - 1), FT * ((int)tid / 9 - 1), fx,
 			                        fy, fz);
 		}
 		__syncthreads();
+		// (a thread takes two neighbouring half cells, bx even and bx + 1: they lie in the same source tile - the block's x halo is
+		// two half cells, the own run 22 - next to each other in its index: one look-up, three loads for two counts)
+		constexpr int ROUNDS = CNT / (2 * T), KEPT = ROUNDS - 1 < 2 ? ROUNDS - 1 : 2;
 #pragma unroll
-		for (int k = 0; k < PER; ++k) {
-			// (the last round's cell coordinates are worked out per work item, not kept in registers across the loop: see `tid`)
-			const int f = (int)(k == PER - 1 ? tid : threadIdx.x) + T * k;
-			uint32_t cnt = 0, src0 = 0;
-			if (f < FB * nrows) {
-				const int bx = f % FB, row = f / FB, by = row % FB, bz = row / FB;
-				const int gx = bx - 1, gy = by - 1, gz = gz0 + bz;
-				const int dx = gx < 0 ? 0 : (gx >= FT ? 2 : 1), dy = gy < 0 ? 0 : (gy >= FT ? 2 : 1), dz = gz < 0 ? 0 : (gz >= FT ? 2 : 1);
+		for (int k = 0; k < ROUNDS; ++k) {
+			// (all but the first KEPT rounds' cell coordinates are worked out per work item, not kept in registers across the loop: see `tid`)
+			const int p = (int)(k >= KEPT ? tid : threadIdx.x) + T * k;
+			uint32_t cnt0 = 0, cnt1 = 0, src0 = 0;
+			if (p < (FBX / 2) * nrows) {
+				const int bx = 2 * (p % (FBX / 2)), row = p / (FBX / 2), by = row % FB, bz = row / FB;
+				const int gx = bx - 2, gy = by - 1, gz = gz0 + bz;
+				const int dx = gx < 0 ? 0 : (gx >= FTX ? 2 : 1), dy = gy < 0 ? 0 : (gy >= FT ? 2 : 1), dz = gz < 0 ? 0 : (gz >= FT ? 2 : 1);
 				const int src = srct[dx + 3 * dy + 9 * dz];
 				if (src >= 0) {
-					const uint32_t fid = (uint32_t)((gx - FT * (dx - 1)) + FT * ((gy - FT * (dy - 1)) + FT * (gz - FT * (dz - 1))));
-					const uint32_t *fs = fine_start + ((uint32_t)src * FT_STRIDE + fid);  // (nt * FT_STRIDE < 2^32 up to 3 M tiles)
+					const uint32_t fid = (uint32_t)((gx - FTX * (dx - 1)) + FTX * ((gy - FT * (dy - 1)) + FT * (gz - FT * (dz - 1))));
+					const uint32_t *fs = fine_start + ((uint32_t)src * FT_STRIDE + fid);  // (nt * FT_STRIDE < 2^32 up to 1.6 M tiles)
 					src0 = fs[0];
-					cnt = fs[1] - src0;
+					const uint32_t mid = fs[1];
+					cnt0 = mid - src0;
+					cnt1 = fs[2] - mid;  // (fid is even: fid + 2 <= FT3)
 				}
-				if (bx <= 1 || bx == FB - 1) rowd[row * 8 + (bx <= 1 ? bx : 2)] = src0;  // (biased by the run's first slot below)
+				// the first cell of each of the row's three runs (biased by the run's first slot below)
+				if (bx == 0 || bx == 2 || bx == FBX - 2) rowd[row * 4 + (bx == 0 ? 0 : (bx == 2 ? 1 : 2))] = src0;
 			}
-			fcnt[f] = cnt;
+			// (a cell of 2^16 - 1 alone exceeds CAP: the part is flagged below)
+			fcnt2[p] = (cnt0 < 0xFFFFu ? cnt0 : 0xFFFFu) | ((cnt1 < 0xFFFFu ? cnt1 : 0xFFFFu) << 16);
 		}
 		__syncthreads();
 		// ---- exclusive scan over the block's fine cells (thread t owns cells PER t .. PER t + PER - 1)
@@ -687,7 +731,7 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			uint32_t len = 0;
 			if (tid < (unsigned)nown_rows) {
 				const int row = (1 + (int)tid % FT) + FB * (1 + (int)tid / FT);
-				len = (uint32_t)foff[row * FB + FB - 1] - (uint32_t)foff[row * FB + 1];
+				len = (uint32_t)foff[row * FBX + FBX - 2] - (uint32_t)foff[row * FBX + 2];
 			}
 			uint32_t in2 = len;
 #pragma unroll
@@ -708,28 +752,29 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 		}
 		// (a crowded part with more own particles than the list holds - it lives in the count array - finds them through the row
 		// offsets instead: uniform)
-		const bool listed = own_total <= 2u * CNT;
-		// ---- the row descriptors: thread r writes row r's, thread t the own-list base of the t-th own row
+		const bool listed = own_total <= (uint32_t)CNT;
+		// ---- the row descriptors: thread r writes row r's, thread t the own-list base of the t-th own row (the top half of the
+		// packed word: two threads share the word, so the second one writes after a barrier)
 		if (tid < (unsigned)nrows) {
 			const int r = (int)tid, by = r % FB, bz = r / FB;
 			const int gy = by - 1, gz = gz0 + bz;
 			const int dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0), dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
 			const int fy = gy - FT * dy, fz = gz - FT * dz;
-			const uint32_t d0 = foff[r * FB], d1 = foff[r * FB + 1], d2 = foff[r * FB + FB - 1];
-			uint32_t *rd = rowd + r * 8;
+			const uint32_t d0 = foff[r * FBX], d1 = foff[r * FBX + 2], d2 = foff[r * FBX + FBX - 2];
+			uint32_t *rd = rowd + r * 4;
 			rd[0] -= d0; rd[1] -= d1; rd[2] -= d2;
 			rd[3] = d1 | (d2 << 16);
-			rd[4] = (uint32_t)(8 * dy); rd[5] = (uint32_t)(8 * dz);
-			rd[6] = (uint32_t)((8 * fy) / FT) | ((uint32_t)((8 * fz) / FT) << 8);
-			if (!(listed && by >= 1 && by <= FT && bz >= 1 && bz <= nzb - 2)) rd[7] = ROW_NOT_OWN;
+			rowe[r] = (uint32_t)((8 * fy) / FT) | ((uint32_t)((8 * fz) / FT) << 3) | ((uint32_t)(8 * (dy + 1)) << 6) |
+			          ((uint32_t)(8 * (dz + 1)) << 11) | ((uint32_t)ROW_NOT_OWN << 16);
 		}
+		__syncthreads();
 		if (listed && tid < (unsigned)nown_rows) {
 			const int row = (1 + (int)tid % FT) + FB * (1 + (int)tid / FT);
-			rowd[row * 8 + 7] = own_first - (uint32_t)foff[row * FB + 1];
+			rowe[row] = (rowe[row] & 0xFFFFu) | ((own_first - (uint32_t)foff[row * FBX + 2]) << 16);
 		}
 		__syncthreads();  // (every count has been read: `own` may overwrite the array)
 		CORR_STAMP(0);  // counts, scans, own offsets
-		// ---- stage the rows: their three runs - one cell of the x-1 tile, the own x tile's eleven, one of the x+1 tile - follow
+		// ---- stage the rows: their three runs - two half cells of the x-1 tile, the own x tile's 22, two of the x+1 tile - follow
 		// each other in the block (positions relative to the own tile's origin, in cells)
 		// Flat: a thread per staged SLOT - every thread's record load is issued at once, CORR_STAGE_DEPTH per thread in flight.
 		// (Round 5 and before: a wave per fine row, one row after the other - 13 dependent HBM round trips per wave and work
@@ -742,8 +787,8 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 		{
 			static_assert(FB_ROWS <= 128, "two row starts per lane");
 			const int rl = (int)(tid & 63u);
-			const uint32_t rs_lo = rl < nrows ? (uint32_t)foff[rl * FB] : 0xFFFFFFFFu;
-			const uint32_t rs_hi = rl + 64 < nrows ? (uint32_t)foff[(rl + 64) * FB] : 0xFFFFFFFFu;
+			const uint32_t rs_lo = rl < nrows ? (uint32_t)foff[rl * FBX] : 0xFFFFFFFFu;
+			const uint32_t rs_hi = rl + 64 < nrows ? (uint32_t)foff[(rl + 64) * FBX] : 0xFFFFFFFFu;
 			auto row_of = [&](uint32_t s) -> int {  // (every lane of the wave calls it, s uniform)
 				return (int)__popcll(__ballot(rs_lo <= s)) + (int)__popcll(__ballot(rs_hi <= s)) - 1;
 			};
@@ -752,23 +797,24 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 				const int span = r_last - r_first;  // (uniform)
 				for (int step = span ? 1 << (31 - __builtin_clz(span)) : 0; step; step >>= 1) {
 					const int c = r + step;
-					if (c <= r_last && (uint32_t)foff[c * FB] <= slot) r = c;
+					if (c <= r_last && (uint32_t)foff[c * FBX] <= slot) r = c;
 				}
-				const uint4 d = *(const uint4 *)(rowd + r * 8);
+				const uint4 d = *(const uint4 *)(rowd + r * 4);
 				const int seg = slot < (d.w & 0xFFFFu) ? 0 : (slot < (d.w >> 16) ? 1 : 2);
 				src = (seg == 0 ? d.x : (seg == 1 ? d.y : d.z)) + slot;
 				rs = r | (seg << 8);
 			};
 			auto put = [&](uint32_t slot, const float4 &rec, int rs) {
 				const int r = rs & 255, seg = rs >> 8;
-				const uint4 d = *(const uint4 *)(rowd + r * 8 + 4);
+				const uint32_t d = rowe[r];
+				const int ob = (int)d >> 16;
 				float t[3];
 				int l[3];
-				fine_decode_at(rec, (int)(d.z & 255u), (int)(d.z >> 8), t, l);
+				fine_decode_at(rec, (int)(d & 7u), (int)((d >> 3) & 7u), t, l);
 				px[slot] = (float)(8 * (seg - 1) + l[0]) + t[0];
-				py[slot] = (float)((int)d.x + l[1]) + t[1];
-				pz[slot] = (float)((int)d.y + l[2]) + t[2];
-				if (seg == 1 && d.w != ROW_NOT_OWN) own[d.w + slot] = (uint16_t)slot;  // the own list: slot order = fine-cell order
+				py[slot] = (float)((int)((d >> 6) & 31u) - 8 + l[1]) + t[1];
+				pz[slot] = (float)((int)((d >> 11) & 31u) - 8 + l[2]) + t[2];
+				if (seg == 1 && ob != ROW_NOT_OWN) own[ob + (int)slot] = (uint16_t)slot;  // the own list: slot order = fine-cell order
 			};
 			// CORR_STAGE_DEPTH records per thread in flight (a dense item stages ~3 600 = 7 per thread)
 			const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
@@ -811,23 +857,23 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 					if (ownoff[mid] <= w) lo = mid;
 					else hi = mid - 1;
 				}
-				me = (uint32_t)foff[((1 + lo % FT) + FB * (1 + lo / FT)) * FB + 1] + (w - ownoff[lo]);
+				me = (uint32_t)foff[((1 + lo % FT) + FB * (1 + lo / FT)) * FBX + 2] + (w - ownoff[lo]);
 			}
 #ifdef CORR_PROFILE
 			const unsigned long long w0_ = wall_clock64();
 #endif
 			const float mx = px[me], my = py[me], mz = pz[me];
 			// block coordinates of its fine cell (the same arithmetic the index was built with: mx = (float)lx + t exactly)
-			int fx = (int)(mx * FT_INV), fy = (int)(my * FT_INV), fz = (int)(mz * FT_INV);
-			fx = fx < FT - 1 ? fx : FT - 1; fy = fy < FT - 1 ? fy : FT - 1; fz = fz < FT - 1 ? fz : FT - 1;
-			const int bx = fx + 1, by = fy + 1, bz = fz - gz0;
+			int fx = (int)(mx * FTX_INV), fy = (int)(my * FT_INV), fz = (int)(mz * FT_INV);
+			fx = fx < FTX - 1 ? fx : FTX - 1; fy = fy < FT - 1 ? fy : FT - 1; fz = fz < FT - 1 ? fz : FT - 1;
+			const int bx = fx + 2, by = fy + 1, bz = fz - gz0;
 			float sx = 0.f, sy = 0.f, sz = 0.f;
 			typedef float f2 __attribute__((ext_vector_type(2)));
 			f2 s2x = 0.f, s2y = 0.f, s2z = 0.f;
 			const float inv_re2 = (float)mp.inv_re2;
 			uint32_t j = 0xFFFFFFFFu;  // (the coincidence hash needs the particle's index: loaded by the rare branch only)
 			const uint32_t myrow = by + FB * bz;
-			const uint32_t grec = rowd[myrow * 8 + 1] + me;
+			const uint32_t grec = rowd[myrow * 4 + 1] + me;
 			auto pair2 = [&](uint32_t q, f2 qx, f2 qy, f2 qz) {
 				const f2 dx = mx - qx, dy = my - qy, dz = mz - qz;
 				const f2 d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
@@ -850,13 +896,13 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 					}
 				}
 			};
-			// The nine x-runs of three fine cells around the particle (always inside the block); `p2` takes two candidates at a time
+			// The nine x-runs of five half cells around the particle (always inside the block); `p2` takes two candidates at a time
 			// (a far-away dummy pads an odd tail: it contributes exactly 0).
 			auto walk = [&](auto &&p2, auto &&p2_centre) {
 				for (int dz = -1; dz <= 1; ++dz)
 					for (int dy = -1; dy <= 1; ++dy) {
-						const int rowf = FB * ((by + dy) + FB * (bz + dz)) + bx;
-						const uint32_t b = foff[rowf - 1], e = foff[rowf + 2];
+						const int rowf = FBX * ((by + dy) + FB * (bz + dz)) + bx;
+						const uint32_t b = foff[rowf - 2], e = foff[rowf + 3];
 						auto run = [&](auto &&pp) {
 							uint32_t q = b;
 							for (; q + 4 <= e; q += 4) {
@@ -920,8 +966,8 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			float tme[3];
 			int lme[3];
 			const float4 rec = spos[grec];
-			const uint32_t yz = rowd[myrow * 8 + 6];
-			fine_decode_at(rec, (int)(yz & 255u), (int)(yz >> 8), tme, lme);
+			const uint32_t yz = rowe[myrow];
+			fine_decode_at(rec, (int)(yz & 7u), (int)((yz >> 3) & 7u), tme, lme);
 			const uint32_t jj = __float_as_uint(rec.w);
 			const int c[3] = {8 * tx + lme[0], 8 * ty + lme[1], 8 * tz + lme[2]};
 			const double spring[3] = {(double)sx, (double)sy, (double)sz};
