@@ -180,7 +180,6 @@ struct lfa_sim {
 	uint8_t *c_unk = nullptr;
 	void *c_pre = nullptr, *c_r = nullptr, *c_x = nullptr, *c_r2 = nullptr, *c_x2 = nullptr, *a2inv = nullptr;
 	void *c_as = nullptr;     // level-1 restriction of A s (fused iteration)
-	void *c_r_cur = nullptr;  // overrides c_r as the coarse right-hand side (parity buffer of the fused iteration)
 	int *slot_l1 = nullptr, *l1_tiles = nullptr, *l1_l2 = nullptr;
 	int n_l1tiles = 0, n2 = 0, a2cap = 0;
 	size_t coarse_elem = 0;
@@ -190,10 +189,6 @@ struct lfa_sim {
 	double last_residual = 0.0;
 	uint64_t last_iters = 0;
 	// lfa_get_solver_stats
-	// single domain, multigrid: the iteration whose residual maxima (cur_rmax_parts, one per workgroup of the AXPY kernel) the
-	// V-cycle's first kernel may test (-1: none) - mg.hip: MgStop
-	int cur_iter = -1, cur_rmax_n = 0;
-	const double *cur_rmax_parts = nullptr;
 	uint64_t stat_launches_iter = 0, stat_transport_iter = 0, stat_transport_solve = 0, stat_mg_levels = 0, stat_mg_first_co = 0;
 	// kernels whose workgroups wait for each other (k_mg_coarse, k_pcg_small): a wait that was given up (mg.hip: co_wait) ends
 	// their use on this handle; the solve that met it is repeated on the launch-per-phase path

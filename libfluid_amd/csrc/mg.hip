@@ -2986,8 +2986,10 @@ template <typename real> static int mg_launch_coarse(lfa_sim *s, int top, void (
 
 /// z = V(r) / scale and the partial sums of dot(z, r) (pcg_grid(n_ptiles) of them) into part_sigma.
 /// `level0_presmoothed`: vq already holds the pre-smoothed iterate (k_mg_axpy_presmooth).
+/// `test`: the stopping rule's inputs for the finest level's residual kernel (pcg.h; `{}`: none).
 /// Executes lfa_mg::plan; `parts` other than MG_PART_ALL (lfa_mg_bench_part) run no level fused into k_mg_coarse's launch.
-template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, bool level0_presmoothed, int parts = MG_PART_ALL) {
+template <typename real>
+static int mg_apply_t(lfa_sim *s, double *part_sigma, bool level0_presmoothed, const lfa_mg_stop &test, int parts = MG_PART_ALL) {
 	lfa_mg &M = *s->mg;
 	const MgPlan &P = M.plan;
 	auto lvl = [&](int l) { return mg_lv<real>(s, l); };
@@ -3040,8 +3042,8 @@ template <typename real> static int mg_apply_t(lfa_sim *s, double *part_sigma, b
 			else {
 				// (the finest level's launch also evaluates the stopping rule on the residual the AXPY kernel has just written)
 				MgStop stop{nullptr, 0, 0, 0.0, nullptr, nullptr};
-				if (l == 0 && level0_presmoothed && D == 0 && s->cur_iter >= 0 && s->cur_rmax_parts)
-					stop = MgStop{s->cur_rmax_parts, s->cur_rmax_n, s->cur_iter, s->prm.tolerance, s->pcg_state, s->pcg_hist};
+				if (l == 0 && level0_presmoothed && D == 0 && test.part_rmax)
+					stop = MgStop{test.part_rmax, test.n_part, test.iter, s->prm.tolerance, s->pcg_state, s->pcg_hist};
 				hipLaunchKernelGGL(k_mg_residual_restrict<real>, dim3(G), dim3(256), 0, s->stream, L, M.lv[l + 1].g, (real *)M.lv[l + 1].b, st, stop);
 			}
 			++launches;
@@ -3092,7 +3094,7 @@ void lfa_mg_stats(const lfa_sim *s, uint64_t *launches_per_cycle, uint64_t *leve
 }
 
 int lfa_mg_apply(lfa_sim *s, double *part_sigma) {
-	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_apply_t<double>(s, part_sigma, false) : mg_apply_t<float>(s, part_sigma, false);
+	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_apply_t<double>(s, part_sigma, false, {}) : mg_apply_t<float>(s, part_sigma, false, {});
 }
 static int mg_plan(lfa_sim *s) {
 	return s->prm.pcg_dtype == LFA_PCG_F64 ? mg_plan_t<double>(s) : mg_plan_t<float>(s);
@@ -3101,8 +3103,8 @@ static int mg_plan(lfa_sim *s) {
 /// One PCG iteration's AXPYs + V-cycle: p += alpha s, r -= alpha q (alpha = sigma / (q.s) from the partials), signed max r
 /// into part_rmax, z = V(r) / scale, partials of dot(z, r) into part_sigma_new. `sdir` = current search direction.
 template <typename real>
-static int mg_axpy_apply_t(lfa_sim *s, const void *sdir, const double *part_sigma, int n_sigma, const double *part_qs, int n_qs,
-                           double *part_rmax, double *part_sigma_new) {
+int lfa_mg_axpy_apply(lfa_sim *s, const void *sdir, const double *part_sigma, int n_sigma, const double *part_qs, int n_qs,
+                      double *part_rmax, double *part_sigma_new, const lfa_mg_stop &stop) {
 	const int *tiles0;
 	const int n0 = lfa_mg_level0(s, &tiles0, nullptr);
 	const int G = mg_grid(n0);
@@ -3110,36 +3112,25 @@ static int mg_axpy_apply_t(lfa_sim *s, const void *sdir, const double *part_sigm
 	                            (const real *)sdir, (real *)s->vr, (real *)s->vq, part_sigma, n_sigma, part_qs, n_qs, part_rmax,
 	                            (const int *)s->pcg_state);
 	LFA_LAUNCH_CHECK(s);
-	return mg_apply_t<real>(s, part_sigma_new, true);
+	return mg_apply_t<real>(s, part_sigma_new, true, stop);
 }
 /// Slab runs, single-reduction CG (k_mg_axpy_presmooth_cg): direction in vs, its image in vs2, w = A z arrives in vq.
 template <typename real>
-static int mg_axpy_apply_cg_t(lfa_sim *s, const double *gamma, int n_gamma, const double *gamma_old, int n_gamma_old, const double *delta,
-                              int n_delta, const double *rmax_prev, int n_rmax, int iter, double *alpha_io, double *part_rmax,
-                              double *part_sigma_new) {
+int lfa_mg_axpy_apply_cg(lfa_sim *s, const double *gamma, int n_gamma, const double *gamma_old, int n_gamma_old, const double *delta,
+                         int n_delta, const double *rmax_prev, int n_rmax, int iter, double *alpha_io, double *part_rmax,
+                         double *part_sigma_new) {
 	const int G = mg_grid(s->n_ptiles);
 	hipLaunchKernelGGL(k_mg_axpy_presmooth_cg<real>, dim3(G), dim3(256), 0, s->stream, (const int *)s->ptiles, s->n_ptiles,
 	                   (const uint8_t *)s->abits, (real *)s->vp, (real *)s->vs, (real *)s->vs2, (const real *)s->vz, (real *)s->vr, (real *)s->vq,
 	                   gamma, n_gamma, gamma_old, n_gamma_old, delta, n_delta, rmax_prev, n_rmax, s->prm.tolerance, iter, alpha_io, part_rmax,
 	                   s->pcg_state, s->pcg_hist);
 	LFA_LAUNCH_CHECK(s);
-	return mg_apply_t<real>(s, part_sigma_new, true);
+	return mg_apply_t<real>(s, part_sigma_new, true, {});
 }
-int lfa_mg_axpy_apply_cg(lfa_sim *s, const double *gamma, int n_gamma, const double *gamma_old, int n_gamma_old, const double *delta,
-                         int n_delta, const double *rmax_prev, int n_rmax, int iter, double *alpha_io, double *part_rmax,
-                         double *part_sigma_new) {
-	return s->prm.pcg_dtype == LFA_PCG_F64
-	           ? mg_axpy_apply_cg_t<double>(s, gamma, n_gamma, gamma_old, n_gamma_old, delta, n_delta, rmax_prev, n_rmax, iter, alpha_io,
-	                                        part_rmax, part_sigma_new)
-	           : mg_axpy_apply_cg_t<float>(s, gamma, n_gamma, gamma_old, n_gamma_old, delta, n_delta, rmax_prev, n_rmax, iter, alpha_io,
-	                                       part_rmax, part_sigma_new);
-}
-int lfa_mg_axpy_apply(lfa_sim *s, const void *sdir, const double *part_sigma, int n_sigma, const double *part_qs, int n_qs,
-                      double *part_rmax, double *part_sigma_new) {
-	return s->prm.pcg_dtype == LFA_PCG_F64
-	           ? mg_axpy_apply_t<double>(s, sdir, part_sigma, n_sigma, part_qs, n_qs, part_rmax, part_sigma_new)
-	           : mg_axpy_apply_t<float>(s, sdir, part_sigma, n_sigma, part_qs, n_qs, part_rmax, part_sigma_new);
-}
+template int lfa_mg_axpy_apply_cg<double>(lfa_sim *, const double *, int, const double *, int, const double *, int, const double *, int, int,
+                                          double *, double *, double *);
+template int lfa_mg_axpy_apply_cg<float>(lfa_sim *, const double *, int, const double *, int, const double *, int, const double *, int, int,
+                                         double *, double *, double *);
 
 /// For lfa_bench_kernel: one part of an iteration on the state left by the last solve. 0: AXPYs + level-0 pre-smoothing,
 /// 1: level-0 residual + restriction, 2: all coarser levels (down, single-workgroup tail, up), 3: level-0 prolongation +
@@ -3263,5 +3254,9 @@ int lfa_mg_bench_part(lfa_sim *s, int part) {
 		return LFA_OK;
 	}
 	const int parts = part == 1 ? MG_PART_DOWN0 : (part == 2 ? MG_PART_COARSE : MG_PART_UP0);
-	return f64 ? mg_apply_t<double>(s, P + PART_SIG1, true, parts) : mg_apply_t<float>(s, P + PART_SIG1, true, parts);
+	return f64 ? mg_apply_t<double>(s, P + PART_SIG1, true, {}, parts) : mg_apply_t<float>(s, P + PART_SIG1, true, {}, parts);
 }
+
+// (behind the function above, the other user of launch_axpy_presmooth: its kernels keep their place in the code object)
+template int lfa_mg_axpy_apply<double>(lfa_sim *, const void *, const double *, int, const double *, int, double *, double *, const lfa_mg_stop &);
+template int lfa_mg_axpy_apply<float>(lfa_sim *, const void *, const double *, int, const double *, int, double *, double *, const lfa_mg_stop &);

@@ -33,10 +33,18 @@ int lfa_dist_refresh_grid(lfa_sim *s, bool with_topology);
 // multigrid preconditioner (mg.hip)
 int lfa_mg_setup(lfa_sim *s);                       // hierarchy for the current unknown set (after lfa_build_rhs)
 int lfa_mg_apply(lfa_sim *s, double *part_sigma);   // vz = V(vr) / scale (vq is scratch), partials of dot(z, r)
-// the AXPYs of a PCG iteration fused with the pre-smoothing of the finest level, then the rest of the V-cycle
+/// Single domain: the residual maxima of iteration `iter` (one per workgroup of the AXPY kernel) that the V-cycle's first kernel
+/// tests against the stopping rule (mg.hip: MgStop). part_rmax == nullptr: no test.
+struct lfa_mg_stop {
+	const double *part_rmax = nullptr;
+	int n_part = 0, iter = 0;
+};
+// the AXPYs of a PCG iteration fused with the pre-smoothing of the finest level, then the rest of the V-cycle (float and double)
+template <typename real>
 int lfa_mg_axpy_apply(lfa_sim *s, const void *sdir, const double *part_sigma, int n_sigma, const double *part_qs, int n_qs,
-                      double *part_rmax, double *part_sigma_new);
+                      double *part_rmax, double *part_sigma_new, const lfa_mg_stop &stop);
 // slab runs: the single-reduction form (gamma = z.r, delta = (A z).z and max r in one collective; mg.hip: k_mg_axpy_presmooth_cg)
+template <typename real>
 int lfa_mg_axpy_apply_cg(lfa_sim *s, const double *gamma, int n_gamma, const double *gamma_old, int n_gamma_old, const double *delta,
                          int n_delta, const double *rmax_prev, int n_rmax, int iter, double *alpha_io, double *part_rmax,
                          double *part_sigma_new);

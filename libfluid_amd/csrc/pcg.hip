@@ -1395,10 +1395,14 @@ static TileCtx iter_ctx(lfa_sim *s) {
 /// number of partial sums the consumers of sigma add up: one per workgroup (+1 for the coarse part of z.r)
 static int sigma_parts(lfa_sim *s) { return pcg_grid(iter_ctx(s).n_ptiles) + (is_ml(s) ? 1 : 0); }
 
-template <typename real> static CoarseFields<real> make_coarse(lfa_sim *s) {
-	CoarseFields<real> cf{s->c_diag, {s->c_w[0], s->c_w[1], s->c_w[2]}, s->c_unk, (real *)s->c_pre,
-	                      s->c_r_cur ? (real *)s->c_r_cur : (real *)s->c_r, (real *)s->c_x};
+/// `r`: the coarse right-hand side - lfa_sim::c_r, or the parity buffer of the fused iteration
+template <typename real> static CoarseFields<real> make_coarse(lfa_sim *s, real *r) {
+	CoarseFields<real> cf{s->c_diag, {s->c_w[0], s->c_w[1], s->c_w[2]}, s->c_unk, (real *)s->c_pre, r, (real *)s->c_x};
 	return cf;
+}
+/// the coarse levels inside a launch of k_mic_apply / k_pcg_b (EMBED): what their PCG_COARSE_BLOCKS workgroups need beside the fields
+static CoarseArgs embedded_coarse(lfa_sim *s) {
+	return CoarseArgs{s->l1_tiles, s->n_l1tiles, s->a2inv, s->c_x2, (double *)s->pcg_hist + 6144, (unsigned *)(s->pcg_state + 4)};
 }
 
 /// Dense SPD inverse by Cholesky (n2 is the number of 64^3-cell aggregates that hold fluid: tens, at most 512).
@@ -1493,7 +1497,7 @@ template <typename real> static int coarse_setup(lfa_sim *s) {
 	hipLaunchKernelGGL(k_coarse_coeffs, dim3(pcg_grid(s->n_ptiles)), dim3(256), 0, s->stream, tc, s->abits, s->slot_l1,
 	                   s->c_diag, s->c_w[0], s->c_w[1], s->c_w[2], s->c_unk);
 	LFA_LAUNCH_CHECK(s);
-	CoarseFields<real> cf = make_coarse<real>(s);
+	CoarseFields<real> cf = make_coarse<real>(s, (real *)s->c_r);
 	const int g1grid = (s->n_l1tiles + PCG_WAVES - 1) / PCG_WAVES;
 	hipLaunchKernelGGL(k_coarse_factor<real>, dim3(g1grid), dim3(256), 0, s->stream, s->l1_tiles, s->n_l1tiles, cf,
 	                   (real)s->a_scale, (real)s->prm.tau, (real)s->prm.sigma);
@@ -1551,8 +1555,9 @@ template <typename real> static int coarse_setup(lfa_sim *s) {
 }
 
 /// Coarse half of z = M^-1 r: level-1 block MIC(0) + dense top level; writes the coarse share of z.r as partial G.
-template <typename real> static int coarse_apply(lfa_sim *s, double *part_sigma, hipStream_t stream) {
-	CoarseFields<real> cf = make_coarse<real>(s);
+/// `r1`: the restricted residual (make_coarse).
+template <typename real> static int coarse_apply(lfa_sim *s, real *r1, double *part_sigma, hipStream_t stream) {
+	CoarseFields<real> cf = make_coarse<real>(s, r1);
 	double *extra = part_sigma + pcg_grid(s->n_ptiles);
 	if (s->n_l1tiles <= 64) {
 		constexpr int WAVES = sizeof(real) == 4 ? 16 : 8;
@@ -1646,10 +1651,9 @@ template <typename real> static int mic_apply(lfa_sim *s, double *part_sigma, bo
 		// more than 64 level-1 blocks) the coarse levels follow as their own launch.
 		const bool embed = is_ml(s) && r1_ready && s->n_l1tiles <= 64;
 		if (embed) {
-			CoarseArgs ca{s->l1_tiles, s->n_l1tiles, s->a2inv, s->c_x2, (double *)s->pcg_hist + 6144, (unsigned *)(s->pcg_state + 4)};
 			hipLaunchKernelGGL((k_mic_apply<real, SWEEP_BOTH, true>), dim3(G + PCG_COARSE_BLOCKS), dim3(256), 0, s->stream, tc,
 			                   (const int *)nullptr, s->n_ptiles, s->abits, v, scale, part_sigma, s->pcg_state, (real *)nullptr,
-			                   (const int *)s->slot_l1, make_coarse<real>(s), ca);
+			                   (const int *)s->slot_l1, make_coarse<real>(s, (real *)s->c_r), embedded_coarse(s));
 			LFA_LAUNCH_CHECK(s);
 		} else {
 			hipLaunchKernelGGL((k_mic_apply<real, SWEEP_BOTH, false>), dim3(G), dim3(256), 0, s->stream, tc,
@@ -1657,7 +1661,7 @@ template <typename real> static int mic_apply(lfa_sim *s, double *part_sigma, bo
 			                   (is_ml(s) && !r1_ready) ? (real *)s->c_r : (real *)nullptr, (const int *)s->slot_l1,
 			                   CoarseFields<real>{}, CoarseArgs{});
 			LFA_LAUNCH_CHECK(s);
-			if (is_ml(s)) LFA_TRY(coarse_apply<real>(s, part_sigma, s->stream));
+			if (is_ml(s)) LFA_TRY(coarse_apply<real>(s, (real *)s->c_r, part_sigma, s->stream));
 		}
 	}
 	return LFA_OK;
@@ -1700,6 +1704,42 @@ static void launch_pcg_a(bool first, bool coarse, int grid, hipStream_t st, Args
 	else if (first) hipLaunchKernelGGL((k_pcg_a<real, true, false>), dim3(grid), dim3(256), 0, st, a...);
 	else if (coarse) hipLaunchKernelGGL((k_pcg_a<real, false, true>), dim3(grid), dim3(256), 0, st, a...);
 	else hipLaunchKernelGGL((k_pcg_a<real, false, false>), dim3(grid), dim3(256), 0, st, a...);
+}
+/// k_pcg_b on `grid` workgroups with the search direction `s_cur`. `embed`: PCG_COARSE_BLOCKS more workgroups run the coarse levels
+/// of the multilevel preconditioner on the restricted residual `cr_cur`; `cr_next` receives the next one.
+template <typename real>
+static void launch_pcg_b(lfa_sim *s, bool embed, int grid, const real *s_cur, const double *sig, int n_sig, const double *zs, int n_zs,
+                         double *sig_new, real *cr_cur, real *cr_next) {
+	const Vecs<real> v = make_vecs<real>(s);
+	const real scale = (real)s->a_scale;
+	double *rmax = s->partials + PART_RMAX;
+	if (embed) {
+		CoarseFields<real> cf = make_coarse<real>(s, cr_cur);
+		cf.as = (const real *)s->c_as;
+		hipLaunchKernelGGL((k_pcg_b<real, true>), dim3(grid + PCG_COARSE_BLOCKS), dim3(256), 0, s->stream, (const int *)s->ptiles,
+		                   s->n_ptiles, s->abits, v, s_cur, scale, sig, n_sig, zs, n_zs, rmax, sig_new, s->pcg_state, cr_next,
+		                   (const int *)s->slot_l1, cf, embedded_coarse(s));
+	} else {
+		hipLaunchKernelGGL((k_pcg_b<real, false>), dim3(grid), dim3(256), 0, s->stream, (const int *)s->ptiles, s->n_ptiles, s->abits,
+		                   v, s_cur, scale, sig, n_sig, zs, n_zs, rmax, sig_new, s->pcg_state, cr_next, (const int *)s->slot_l1,
+		                   CoarseFields<real>{}, CoarseArgs{});
+	}
+}
+
+/// Slabs: a boundary tile layer whose rows couple to the neighbour rank: its tiles, the slot of the first, the workgroups of its
+/// launch, and where their partials of q.s go among those of the two faces.
+struct FaceRows { int n, slot0, g, part; };
+/// The rows of q = A vec that needed vec from across the slab faces ([0] the lower, [1] the upper), once the slices have been
+/// exchanged; `c_as`: the level-1 restriction of q (or null), `part`: the faces' partials of q.s (behind those of k_pcg_a).
+template <typename real> static int ghost_face_rows(lfa_sim *s, const FaceRows (&faces)[2], const real *vec, real *c_as, double *part) {
+	for (int f = 0; f < 2; ++f) {
+		if (!faces[f].g) continue;
+		hipLaunchKernelGGL(k_ghost_face_rows<real>, dim3(faces[f].g), dim3(256), 0, s->stream, make_ctx(s), f == 0 ? faces[f].n : 0,
+		                   faces[f].slot0, f == 1 ? faces[f].n : 0, s->abits, vec, (real *)s->vq, (real)s->a_scale, part + faces[f].part, c_as,
+		                   (const int *)s->slot_l1, s->pcg_state);
+		LFA_LAUNCH_CHECK(s);
+	}
+	return LFA_OK;
 }
 
 /// Launch widths (workgroups) of k_pcg_a / k_pcg_b. k_pcg_a streams: it is sized to be resident at once (4 workgroups per
@@ -1744,6 +1784,15 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	const bool dist = s->dist != nullptr;
 	int init_state[4] = {-1, 0, 0, 0};
 	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, 16, hipMemcpyHostToDevice, s->stream));
+	// how a solve whose right-hand side is zero ends, whether the host or the device found it so
+	auto finish_zero_rhs = [&]() -> int {
+		if (s->warm_started) {  // the reference returns p = 0 here (src/pressure_solver.cpp:33-35), not the guess
+			hipLaunchKernelGGL((k_warm_residual<real, true>), dim3(G), dim3(256), 0, s->stream, tc, v.r, (const real *)v.q, v.p);
+			LFA_LAUNCH_CHECK(s);
+		}
+		s->pressure_epoch = s->solve_epoch;
+		return LFA_OK;
+	};
 	// early out: sum b^2 < 1e-6 (src/pressure_solver.cpp:29-35). Single domain: decided on the device (k_check_rhs marks the solve
 	// done, every kernel below is a no-op then, the host learns it at its first poll) - unless the previous solve ended that way: a
 	// scene at rest would queue a chunk of no-op iterations step after step, so it asks first, as slab runs (whose sum is a
@@ -1768,11 +1817,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		}
 		s->last_rhs_zero = tot < 1e-6;
 		if (tot < 1e-6) {
-			if (s->warm_started) {  // the reference returns p = 0 here (src/pressure_solver.cpp:33-35), not the guess
-				hipLaunchKernelGGL((k_warm_residual<real, true>), dim3(G), dim3(256), 0, s->stream, tc, v.r, (const real *)v.q, v.p);
-				LFA_LAUNCH_CHECK(s);
-			}
-			s->pressure_epoch = s->solve_epoch;
+			LFA_TRY(finish_zero_rhs());
 			return LFA_OK;
 		}
 	} else {
@@ -1796,17 +1841,13 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	// where the consumers find a reduced scalar: the per-workgroup partials (they re-add them in a fixed order), or -
 	// with slabs - the all-reduced value
 	double *red = s->dist_red;
-	auto sig_src = [&](int parity) { return dist ? red + 3 + parity : P + (parity ? PART_SIG1 : PART_SIG0); };
-	const int n_sig = dist ? 1 : NS, n_zs = dist ? 1 : G, n_max = dist ? 1 : G;
+	auto sig_part = [&](int parity) { return P + (parity ? PART_SIG1 : PART_SIG0); };
+	auto sig_src = [&](int parity) { return dist ? red + 3 + parity : sig_part(parity); };
+	const int n_sig = dist ? 1 : NS, n_zs = dist ? 1 : G;
 	const real *cx = is_ml(s) ? (const real *)s->c_x : (const real *)nullptr;
 	// z = M^-1 r ; s = z ; sigma = z.r
 	LFA_TRY(mic_apply<real>(s, P + PART_SIG0));
 	if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_SIG0, NS, 3, false));
-	const int maxit = (int)s->prm.max_iterations;
-	const int chunk = 4;
-	int done = -1, nan = 0, i = 0;
-	int *hstate = (int *)s->h_pinned;
-	int aborted = 0;  // a kernel whose workgroups wait for each other gave a wait up (mg.hip: co_wait)
 	// fused iteration (k_pcg_a / k_pcg_b): tile-local MIC(0) with or without the coarse levels, single domain or slabs
 	// (with the multigrid preconditioner the second kernel is the AXPY/pre-smoothing kernel followed by the V-cycle, mg.hip)
 	const bool fused = (is_mg(s) || s->prm.pcg_fused) && s->prm.precond != LFA_PRECOND_MIC0_EXACT && (s->n_ptiles == 0 || s->nbr_table);
@@ -1818,193 +1859,150 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	const bool embed = fused && is_ml(s) && s->n_l1tiles <= 64;
 	real *sbuf[2] = {(real *)s->vs, (real *)s->vs2};
 	real *crbuf[2] = {(real *)s->c_r, is_ml(s) ? (real *)s->c_r + s->ncp1 : (real *)nullptr};
+	real *cas = is_ml(s) ? (real *)s->c_as : (real *)nullptr;
 	// launch widths of the two fused kernels (workgroups); each kernel reads the other's per-workgroup partials
 	int GA, GB;
 	fused_grids(G, GA, GB);
 	if (is_mg(s)) GB = G;  // the V-cycle kernels write pcg_grid(n_ptiles) partials
 	const int NSB = GB + (is_ml(s) ? 1 : 0);
+	const int nr = dist ? s->dist->nranks : 0;
 	// slabs: boundary tile layers whose rows couple to the neighbour rank (k_ghost_face_rows)
 	const int n_face_lo = dist && lfa_has_lo(s) ? s->n_own_first : 0, n_face_hi = dist && lfa_has_hi(s) ? s->n_own_last : 0;
 	const int g_face_lo = std::min(16, (n_face_lo + PCG_WAVES - 1) / PCG_WAVES), g_face_hi = std::min(16, (n_face_hi + PCG_WAVES - 1) / PCG_WAVES);
+	const FaceRows faces[2] = {{n_face_lo, 0, g_face_lo, 0}, {n_face_hi, s->n_ptiles - n_face_hi, g_face_hi, g_face_lo}};
+	const int G_ZS = GA + g_face_lo + g_face_hi;  // partials of q.s of one iteration
+	double *face_parts = P + PART_ZS + GA;
 	// Slab runs with the multigrid preconditioner: the single-reduction form of CG (Chronopoulos / Gear; mg.hip:
 	// k_mg_axpy_presmooth_cg). Step A_k: w = A z_k and delta_k = w.z_k (k_pcg_a without a search direction, the slice of z across
 	// the slab faces, the rows that needed it), then gamma_k = z_k.r_k, delta_k and the signed max of r_k of every rank in ONE
 	// collective (gather buffer k & 1). Step B_k: stopping rule on r_k, the recurrences, r_k+1, the V-cycle -> z_k+1.
 	// Per iteration 2 D + 2 transport calls (D distributed levels) instead of 2 D + 3.
 	const bool cg1 = fused && dist && is_mg(s);
-	if (cg1) {
-		const int nr = s->dist->nranks;
-		double *alpha_io = s->dist_red + LFA_DIST_ALPHA_OFF;
-		auto step_a = [&](int k, const double *rmax_part, int n_rmax_part, const double *gam_part, int n_gam_part) -> int {
-			launch_pcg_a<real>(true, false, GA, s->stream, s->n_ptiles, (const int *)s->nbr_table, (const uint8_t *)s->abits, (const real *)v.z,
-			                   (const real *)nullptr, (real *)nullptr, v.q, scale, (const double *)nullptr, 0, (const double *)nullptr, 0,
-			                   (const double *)nullptr, 0, s->prm.tolerance, 0, s->pcg_state, s->pcg_hist, P + PART_ZS, (const real *)nullptr,
-			                   (const real *)nullptr, (real *)nullptr);
-			LFA_LAUNCH_CHECK(s);
-			LFA_TRY(lfa_dist_exchange_slices(s, v.z, (int)sizeof(real)));
-			if (g_face_lo) {
-				hipLaunchKernelGGL(k_ghost_face_rows<real>, dim3(g_face_lo), dim3(256), 0, s->stream, tc, n_face_lo, 0, 0, s->abits,
-				                   (const real *)v.z, v.q, scale, P + PART_ZS + GA, (real *)nullptr, (const int *)s->slot_l1, s->pcg_state);
-				LFA_LAUNCH_CHECK(s);
-			}
-			if (g_face_hi) {
-				hipLaunchKernelGGL(k_ghost_face_rows<real>, dim3(g_face_hi), dim3(256), 0, s->stream, tc, 0, s->n_ptiles - n_face_hi,
-				                   n_face_hi, s->abits, (const real *)v.z, v.q, scale, P + PART_ZS + GA + g_face_lo, (real *)nullptr,
-				                   (const int *)s->slot_l1, s->pcg_state);
-				LFA_LAUNCH_CHECK(s);
-			}
-			return lfa_dist_gather_triple(s, rmax_part, n_rmax_part, gam_part, n_gam_part, P + PART_ZS, GA + g_face_lo + g_face_hi, k & 1);
-		};
-		const uint64_t calls_a0 = s->dist->calls;
-		LFA_TRY(step_a(0, P + PART_RMAX, 0, P + PART_SIG0, NS));
-		const uint64_t calls_a = s->dist->calls - calls_a0;
-		while (!aborted && i < maxit && done < 0) {
-			const int end = std::min(maxit, i + (i == 0 ? first_chunk : chunk));
-			for (; i < end; ++i) {
-				const int po = i & 1, pn = po ^ 1;
-				const uint64_t calls0 = s->dist->calls;
-				const double *cur = lfa_dist_gather_buf(s, po), *old = lfa_dist_gather_buf(s, pn);
-				double *sig_new_part = P + (pn ? PART_SIG1 : PART_SIG0);
-				LFA_TRY(lfa_mg_axpy_apply_cg(s, cur + nr, nr, old + nr, nr, cur + 2 * nr, nr, cur, nr, i, alpha_io, P + PART_RMAX, sig_new_part));
-				LFA_TRY(step_a(i + 1, P + PART_RMAX, GB, sig_new_part, NSB));
-				if (i == 0) {
-					s->stat_transport_iter = s->dist->calls - calls0;
-					uint64_t mgl = 0;
-					lfa_mg_stats(s, &mgl, &s->stat_mg_levels, &s->stat_mg_first_co);
-					s->stat_launches_iter = 1 + (g_face_lo > 0) + (g_face_hi > 0) + mgl;
-				}
-			}
-			hipLaunchKernelGGL(k_check_converged, dim3(1), dim3(256), 0, s->stream, (const double *)lfa_dist_gather_buf(s, i & 1), nr,
-			                   s->prm.tolerance, i - 1, s->pcg_state, s->pcg_hist, (const double *)lfa_dist_gather_buf(s, i & 1) + 3 * nr);
-			LFA_LAUNCH_CHECK(s);
-			LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, 80, hipMemcpyDeviceToHost, s->stream));
-			LFA_HIP(s, hipStreamSynchronize(s->stream));
-			done = hstate[0];
-			nan = hstate[1];
-			aborted = hstate[2];
-			if (aborted) break;
-		}
-		(void)calls_a;
-	}
-	while (fused && !cg1 && !aborted && i < maxit && done < 0) {
-		const int end = std::min(maxit, i + (i == 0 ? first_chunk : chunk));
-		for (; i < end; ++i) {
-			const int po = i & 1, pn = po ^ 1;
-			const uint64_t calls0 = dist ? s->dist->calls : 0;
-			// where a kernel finds the scalars of the previous one: per-workgroup partials (the application before the loop
-			// wrote NS sigma partials, k_pcg_b writes NSB), or - with slabs - the all-reduced values
-			// slabs: sigma_k (k >= 1) and the signed max of the residual it belongs to arrive together, one value per rank
-			// (lfa_dist_gather_pair, parity k & 1); sigma_0 of the application before the loop is the all-reduced scalar
-			const int nr = dist ? s->dist->nranks : 0;
-			const double *sig_po = !dist ? P + (po ? PART_SIG1 : PART_SIG0) : (i == 0 ? red + 3 : lfa_dist_gather_buf(s, po) + nr);
-			const double *sig_pn = !dist ? P + (pn ? PART_SIG1 : PART_SIG0) : (i <= 1 ? red + 3 : lfa_dist_gather_buf(s, pn) + nr);
-			const int n_sig_po = dist ? (i == 0 ? 1 : nr) : (i == 0 ? NS : NSB), n_sig_pn = dist ? (i <= 1 ? 1 : nr) : (i <= 1 ? NS : NSB);
-			const double *rmax_prev = !dist ? P + PART_RMAX : (i == 0 ? red + 2 : lfa_dist_gather_buf(s, po));
-			const int n_rmax_prev = dist ? (i == 0 ? 1 : nr) : GB;
-			launch_pcg_a<real>(i == 0, is_ml(s), GA, s->stream, n_it, (const int *)s->nbr_table, (const uint8_t *)s->abits,
-			                   (const real *)v.z, (const real *)sbuf[po], sbuf[pn], v.q, scale, sig_po, n_sig_po, sig_pn, n_sig_pn,
-			                   rmax_prev, n_rmax_prev, s->prm.tolerance, i, s->pcg_state,
-			                   s->pcg_hist, P + PART_ZS, cx, (const real *)s->c_x2, is_ml(s) ? (real *)s->c_as : (real *)nullptr);
-			LFA_LAUNCH_CHECK(s);
-			if (dist) {
-				// the new search direction across the slab faces, then the rows of q that needed it
-				LFA_TRY(lfa_dist_exchange_slices(s, sbuf[pn], (int)sizeof(real)));
-				real *cas = is_ml(s) ? (real *)s->c_as : (real *)nullptr;
-				if (g_face_lo) {
-					hipLaunchKernelGGL(k_ghost_face_rows<real>, dim3(g_face_lo), dim3(256), 0, s->stream, tc, n_face_lo, 0, 0, s->abits,
-					                   (const real *)sbuf[pn], v.q, scale, P + PART_ZS + GA, cas, (const int *)s->slot_l1, s->pcg_state);
-					LFA_LAUNCH_CHECK(s);
-				}
-				if (g_face_hi) {
-					hipLaunchKernelGGL(k_ghost_face_rows<real>, dim3(g_face_hi), dim3(256), 0, s->stream, tc, 0, s->n_ptiles - n_face_hi,
-					                   n_face_hi, s->abits, (const real *)sbuf[pn], v.q, scale, P + PART_ZS + GA + g_face_lo, cas,
-					                   (const int *)s->slot_l1, s->pcg_state);
-					LFA_LAUNCH_CHECK(s);
-				}
-				LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, GA + g_face_lo + g_face_hi, 1, false));
-			}
-			const double *zs_src = dist ? red + 1 : P + PART_ZS;
-			const int n_zs_src = dist ? 1 : GA;
-			double *sig_new_part = P + (pn ? PART_SIG1 : PART_SIG0);
-			CoarseFields<real> cf = is_ml(s) ? make_coarse<real>(s) : CoarseFields<real>{};
-			if (is_mg(s)) {
-				// (single domain: the V-cycle's first kernel tests the residual this AXPY produces - the reference does not
-				// precondition a converged residual either)
-				s->cur_iter = dist ? -1 : i;
-				s->cur_rmax_parts = P + PART_RMAX;
-				s->cur_rmax_n = GB;
-				const int rc_mg = lfa_mg_axpy_apply(s, sbuf[pn], sig_po, n_sig_po, zs_src, n_zs_src, P + PART_RMAX, sig_new_part);
-				s->cur_iter = -1;
-				LFA_TRY(rc_mg);
-			} else if (embed) {
-				cf.r = crbuf[po];
-				cf.as = (const real *)s->c_as;
-				CoarseArgs ca{s->l1_tiles, s->n_l1tiles, s->a2inv, s->c_x2, (double *)s->pcg_hist + 6144, (unsigned *)(s->pcg_state + 4)};
-				hipLaunchKernelGGL((k_pcg_b<real, true>), dim3(GB + PCG_COARSE_BLOCKS), dim3(256), 0, s->stream,
-				                   (const int *)s->ptiles, s->n_ptiles, s->abits, v, (const real *)sbuf[pn], scale, sig_po, n_sig_po,
-				                   zs_src, n_zs_src, P + PART_RMAX, sig_new_part, s->pcg_state, crbuf[pn], (const int *)s->slot_l1, cf, ca);
-				LFA_LAUNCH_CHECK(s);
-			} else {
-				hipLaunchKernelGGL((k_pcg_b<real, false>), dim3(GB), dim3(256), 0, s->stream, (const int *)s->ptiles,
-				                   s->n_ptiles, s->abits, v, (const real *)sbuf[pn], scale, sig_po, n_sig_po, zs_src, n_zs_src,
-				                   P + PART_RMAX, sig_new_part, s->pcg_state, crbuf[pn], (const int *)s->slot_l1,
-				                   CoarseFields<real>{}, CoarseArgs{});
-				LFA_LAUNCH_CHECK(s);
-				if (is_ml(s)) {  // more than 64 level-1 blocks: the coarse levels follow as their own launches
-					s->c_r_cur = crbuf[pn];
-					LFA_TRY(coarse_apply<real>(s, sig_new_part + GB - G, s->stream));
-					s->c_r_cur = nullptr;
-				}
-			}
-			if (dist) LFA_TRY(lfa_dist_gather_pair(s, P + PART_RMAX, GB, sig_new_part, NSB, pn));  // one collective for both
-			if (i == 0) {  // lfa_get_solver_stats: every iteration issues the same launches and transport calls
-				s->stat_transport_iter = dist ? s->dist->calls - calls0 : 0;
-				uint64_t mgl = 0;
-				if (is_mg(s)) lfa_mg_stats(s, &mgl, &s->stat_mg_levels, &s->stat_mg_first_co);
-				s->stat_launches_iter = 1 + (dist ? (g_face_lo > 0) + (g_face_hi > 0) : 0) + (is_mg(s) ? mgl : 1);
-			}
-		}
-		// the residual of the last iteration of the chunk is tested here (k_pcg_a tests the one before it)
-		hipLaunchKernelGGL(k_check_converged, dim3(1), dim3(256), 0, s->stream,
-		                   dist ? (const double *)lfa_dist_gather_buf(s, i & 1) : P + PART_RMAX, dist ? s->dist->nranks : GB,
-		                   s->prm.tolerance, i - 1, s->pcg_state, s->pcg_hist,
-		                   dist ? (const double *)lfa_dist_gather_buf(s, i & 1) + 3 * s->dist->nranks : (const double *)nullptr);
+	auto step_a = [&](int k, const double *rmax_part, int n_rmax_part, const double *gam_part, int n_gam_part) -> int {
+		launch_pcg_a<real>(true, false, GA, s->stream, s->n_ptiles, (const int *)s->nbr_table, (const uint8_t *)s->abits, (const real *)v.z,
+		                   (const real *)nullptr, (real *)nullptr, v.q, scale, (const double *)nullptr, 0, (const double *)nullptr, 0,
+		                   (const double *)nullptr, 0, s->prm.tolerance, 0, s->pcg_state, s->pcg_hist, P + PART_ZS, (const real *)nullptr,
+		                   (const real *)nullptr, (real *)nullptr);
 		LFA_LAUNCH_CHECK(s);
+		LFA_TRY(lfa_dist_exchange_slices(s, v.z, (int)sizeof(real)));
+		LFA_TRY(ghost_face_rows<real>(s, faces, v.z, nullptr, face_parts));
+		return lfa_dist_gather_triple(s, rmax_part, n_rmax_part, gam_part, n_gam_part, P + PART_ZS, G_ZS, k & 1);
+	};
+	auto step_cg1 = [&](int i) -> int {
+		const int po = i & 1, pn = po ^ 1;
+		const double *cur = lfa_dist_gather_buf(s, po), *old = lfa_dist_gather_buf(s, pn);
+		LFA_TRY(lfa_mg_axpy_apply_cg<real>(s, cur + nr, nr, old + nr, nr, cur + 2 * nr, nr, cur, nr, i, s->dist_red + LFA_DIST_ALPHA_OFF,
+		                                   P + PART_RMAX, sig_part(pn)));
+		return step_a(i + 1, P + PART_RMAX, GB, sig_part(pn), NSB);
+	};
+	auto step_fused = [&](int i) -> int {
+		const int po = i & 1, pn = po ^ 1;
+		// where a kernel finds the scalars of the previous one: per-workgroup partials (the application before the loop
+		// wrote NS sigma partials, k_pcg_b writes NSB), or - with slabs - the all-reduced values
+		// slabs: sigma_k (k >= 1) and the signed max of the residual it belongs to arrive together, one value per rank
+		// (lfa_dist_gather_pair, parity k & 1); sigma_0 of the application before the loop is the all-reduced scalar
+		const double *sig_po = !dist ? sig_part(po) : (i == 0 ? red + 3 : lfa_dist_gather_buf(s, po) + nr);
+		const double *sig_pn = !dist ? sig_part(pn) : (i <= 1 ? red + 3 : lfa_dist_gather_buf(s, pn) + nr);
+		const int n_sig_po = dist ? (i == 0 ? 1 : nr) : (i == 0 ? NS : NSB), n_sig_pn = dist ? (i <= 1 ? 1 : nr) : (i <= 1 ? NS : NSB);
+		const double *rmax_prev = !dist ? P + PART_RMAX : (i == 0 ? red + 2 : lfa_dist_gather_buf(s, po));
+		const int n_rmax_prev = dist ? (i == 0 ? 1 : nr) : GB;
+		launch_pcg_a<real>(i == 0, is_ml(s), GA, s->stream, n_it, (const int *)s->nbr_table, (const uint8_t *)s->abits,
+		                   (const real *)v.z, (const real *)sbuf[po], sbuf[pn], v.q, scale, sig_po, n_sig_po, sig_pn, n_sig_pn,
+		                   rmax_prev, n_rmax_prev, s->prm.tolerance, i, s->pcg_state,
+		                   s->pcg_hist, P + PART_ZS, cx, (const real *)s->c_x2, cas);
+		LFA_LAUNCH_CHECK(s);
+		if (dist) {
+			// the new search direction across the slab faces, then the rows of q that needed it
+			LFA_TRY(lfa_dist_exchange_slices(s, sbuf[pn], (int)sizeof(real)));
+			LFA_TRY(ghost_face_rows<real>(s, faces, sbuf[pn], cas, face_parts));
+			LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G_ZS, 1, false));
+		}
+		const double *zs_src = dist ? red + 1 : P + PART_ZS;
+		const int n_zs_src = dist ? 1 : GA;
+		if (is_mg(s)) {
+			// (single domain: the V-cycle's first kernel tests the residual this AXPY produces - the reference does not
+			// precondition a converged residual either)
+			LFA_TRY(lfa_mg_axpy_apply<real>(s, sbuf[pn], sig_po, n_sig_po, zs_src, n_zs_src, P + PART_RMAX, sig_part(pn),
+			                                dist ? lfa_mg_stop{} : lfa_mg_stop{P + PART_RMAX, GB, i}));
+		} else {
+			launch_pcg_b<real>(s, embed, GB, sbuf[pn], sig_po, n_sig_po, zs_src, n_zs_src, sig_part(pn), crbuf[po], crbuf[pn]);
+			LFA_LAUNCH_CHECK(s);
+			// more than 64 level-1 blocks: the coarse levels follow as their own launches
+			if (is_ml(s) && !embed) LFA_TRY(coarse_apply<real>(s, crbuf[pn], sig_part(pn) + GB - G, s->stream));
+		}
+		if (dist) LFA_TRY(lfa_dist_gather_pair(s, P + PART_RMAX, GB, sig_part(pn), NSB, pn));  // one collective for both
+		return LFA_OK;
+	};
+	// The stopping rule on the residual of iteration `it` (k_check_converged), read where the form leaves its signed maxima: the
+	// workgroups' partials, or - slabs - the gathered values of every rank (fused, with the ranks' "a wait was given up") or the all-reduced one.
+	auto test_residual = [&](int it) -> int {
+		const double *rmax = P + PART_RMAX, *gave_up = nullptr;
+		int n = fused ? GB : G;
+		if (dist && fused) {
+			rmax = lfa_dist_gather_buf(s, (it + 1) & 1);
+			n = nr;
+			gave_up = rmax + 3 * nr;
+		} else if (dist) {
+			rmax = red + 2;
+			n = 1;
+		}
+		hipLaunchKernelGGL(k_check_converged, dim3(1), dim3(256), 0, s->stream, rmax, n, s->prm.tolerance, it, s->pcg_state, s->pcg_hist, gave_up);
+		LFA_LAUNCH_CHECK(s);
+		return LFA_OK;
+	};
+	auto step_unfused = [&](int i) -> int {
+		const int po = i & 1, pn = po ^ 1;
+		if (dist) LFA_TRY(lfa_dist_exchange_slices(s, v.s, (int)sizeof(real)));  // search vector across the slab faces
+		hipLaunchKernelGGL(k_spmv<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, (const real *)v.s, v.z, scale,
+		                   P + PART_ZS, s->pcg_state);
+		LFA_LAUNCH_CHECK(s);
+		if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G, 1, false));
+		hipLaunchKernelGGL(k_axpy_max<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, v, sig_src(po), n_sig,
+		                   dist ? red + 1 : P + PART_ZS, n_zs, P + PART_RMAX, s->pcg_state,
+		                   is_ml(s) ? (real *)s->c_r : (real *)nullptr, (const int *)s->slot_l1);
+		LFA_LAUNCH_CHECK(s);
+		if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_RMAX, G, 2, true));
+		LFA_TRY(test_residual(i));
+		LFA_TRY(mic_apply<real>(s, sig_part(pn), true));
+		if (dist) LFA_TRY(lfa_dist_allreduce(s, sig_part(pn), NS, 3 + pn, false));
+		hipLaunchKernelGGL(k_update_s<real>, dim3(G), dim3(256), 0, s->stream, tc, v, sig_src(pn), sig_src(po), n_sig, 0,
+		                   s->pcg_state, s->abits, cx, (const int *)s->slot_l1, (const real *)s->c_x2, (const int *)s->l1_l2);
+		LFA_LAUNCH_CHECK(s);
+		return LFA_OK;
+	};
+	const int maxit = (int)s->prm.max_iterations;
+	const int chunk = 4;
+	int done = -1, nan = 0, i = 0;
+	int *hstate = (int *)s->h_pinned;
+	int aborted = 0;  // a kernel whose workgroups wait for each other gave a wait up (mg.hip: co_wait)
+	// Between chunks the host reads the state words. The fused forms test the residual of the chunk's last iteration first (k_pcg_a
+	// tests the one before it); the launch-per-operation form has tested it inside the iteration and only reads back. No kernel of
+	// that form waits for another, so `aborted` stays 0 there.
+	auto poll = [&]() -> int {
+		if (fused) LFA_TRY(test_residual(i - 1));
 		LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, 80, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
 		done = hstate[0];
 		nan = hstate[1];
 		aborted = hstate[2];
-		if (aborted) break;
-	}
-	while (!fused && !aborted && i < maxit && done < 0) {
+		return LFA_OK;
+	};
+	const int form = cg1 ? 2 : fused ? 1 : 0;  // the iteration step: chosen here, once
+	if (cg1) LFA_TRY(step_a(0, P + PART_RMAX, 0, P + PART_SIG0, NS));
+	while (!aborted && i < maxit && done < 0) {
 		const int end = std::min(maxit, i + (i == 0 ? first_chunk : chunk));
 		for (; i < end; ++i) {
-			const int po = i & 1, pn = po ^ 1;
-			double *sig_new_part = P + (pn ? PART_SIG1 : PART_SIG0);
-			if (dist) LFA_TRY(lfa_dist_exchange_slices(s, v.s, (int)sizeof(real)));  // search vector across the slab faces
-			hipLaunchKernelGGL(k_spmv<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, (const real *)v.s, v.z, scale,
-			                   P + PART_ZS, s->pcg_state);
-			LFA_LAUNCH_CHECK(s);
-			if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G, 1, false));
-			hipLaunchKernelGGL(k_axpy_max<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, v, sig_src(po), n_sig,
-			                   dist ? red + 1 : P + PART_ZS, n_zs, P + PART_RMAX, s->pcg_state,
-			                   is_ml(s) ? (real *)s->c_r : (real *)nullptr, (const int *)s->slot_l1);
-			LFA_LAUNCH_CHECK(s);
-			if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_RMAX, G, 2, true));
-			hipLaunchKernelGGL(k_check_converged, dim3(1), dim3(256), 0, s->stream, dist ? red + 2 : P + PART_RMAX, n_max,
-			                   s->prm.tolerance, i, s->pcg_state, s->pcg_hist, (const double *)nullptr);
-			LFA_LAUNCH_CHECK(s);
-			LFA_TRY(mic_apply<real>(s, sig_new_part, true));
-			if (dist) LFA_TRY(lfa_dist_allreduce(s, sig_new_part, NS, 3 + pn, false));
-			hipLaunchKernelGGL(k_update_s<real>, dim3(G), dim3(256), 0, s->stream, tc, v, sig_src(pn), sig_src(po), n_sig, 0,
-			                   s->pcg_state, s->abits, cx, (const int *)s->slot_l1, (const real *)s->c_x2, (const int *)s->l1_l2);
-			LFA_LAUNCH_CHECK(s);
+			const uint64_t calls0 = dist ? s->dist->calls : 0;
+			LFA_TRY(form == 2 ? step_cg1(i) : form == 1 ? step_fused(i) : step_unfused(i));
+			// lfa_get_solver_stats: every iteration issues the same launches and transport calls (the launch-per-operation form reports none)
+			if (i == 0 && fused) {
+				s->stat_transport_iter = dist ? s->dist->calls - calls0 : 0;
+				uint64_t second = 1;  // k_pcg_b, or the launches of the AXPY kernel and the V-cycle
+				if (is_mg(s)) lfa_mg_stats(s, &second, &s->stat_mg_levels, &s->stat_mg_first_co);
+				s->stat_launches_iter = 1 + (g_face_lo > 0) + (g_face_hi > 0) + second;
+			}
 		}
-		LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, 80, hipMemcpyDeviceToHost, s->stream));
-		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		done = hstate[0];
-		nan = hstate[1];
+		LFA_TRY(poll());
 	}
 	if (aborted) {
 		// What the wait was for never came (a workgroup that is not resident: another process's kernel of the same kind on this GPU,
@@ -2026,11 +2024,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		}
 		s->last_rhs_zero = hstate[3] == 1;
 		if (hstate[3] == 1) {
-			if (s->warm_started) {  // the reference returns p = 0 here (src/pressure_solver.cpp:33-35), not the guess
-				hipLaunchKernelGGL((k_warm_residual<real, true>), dim3(G), dim3(256), 0, s->stream, tc, v.r, (const real *)v.q, v.p);
-				LFA_LAUNCH_CHECK(s);
-			}
-			s->pressure_epoch = s->solve_epoch;
+			LFA_TRY(finish_zero_rhs());
 			return LFA_OK;
 		}
 	}
@@ -2254,7 +2248,7 @@ template <typename real> static int bench_launch(lfa_sim *s, int which) {
 		break;
 	case LFA_K_COARSE:
 		if (!is_ml(s)) return lfa_fail(s, LFA_E_INVALID, "no coarse levels with this preconditioner");
-		return coarse_apply<real>(s, P + PART_SIG1, s->stream);
+		return coarse_apply<real>(s, (real *)s->c_r, P + PART_SIG1, s->stream);
 	case LFA_K_PCG_A:
 		if (!s->nbr_table || !(s->prm.pcg_fused || is_mg(s))) return lfa_fail(s, LFA_E_INVALID, "fused kernels: solve with pcg_fused = 1 first");
 		launch_pcg_a<real>(false, is_ml(s), is_mg(s) ? G : GA, s->stream, n_it, (const int *)s->nbr_table, (const uint8_t *)s->abits,
@@ -2265,20 +2259,9 @@ template <typename real> static int bench_launch(lfa_sim *s, int which) {
 		break;
 	case LFA_K_PCG_B: {
 		if (!s->nbr_table || !s->prm.pcg_fused) return lfa_fail(s, LFA_E_INVALID, "fused kernels: solve with pcg_fused = 1 first");
-		const bool embed = is_ml(s) && s->n_l1tiles <= 64;
 		real *cr1 = is_ml(s) ? (real *)s->c_r + s->ncp1 : (real *)nullptr;
-		if (embed) {
-			CoarseFields<real> cf = make_coarse<real>(s);
-			cf.as = (const real *)s->c_as;
-			CoarseArgs ca{s->l1_tiles, s->n_l1tiles, s->a2inv, s->c_x2, (double *)s->pcg_hist + 6144, (unsigned *)(s->pcg_state + 4)};
-			hipLaunchKernelGGL((k_pcg_b<real, true>), dim3(GB + PCG_COARSE_BLOCKS), dim3(256), 0, s->stream,
-			                   (const int *)s->ptiles, s->n_ptiles, s->abits, v, (const real *)s->vs2, scale, P + PART_SIG0, G, P + PART_ZS, G, P + PART_RMAX, P + PART_SIG1,
-			                   s->pcg_state, cr1, (const int *)s->slot_l1, cf, ca);
-		} else {
-			hipLaunchKernelGGL((k_pcg_b<real, false>), dim3(GB), dim3(256), 0, s->stream, (const int *)s->ptiles, s->n_ptiles,
-			                   s->abits, v, (const real *)s->vs2, scale, P + PART_SIG0, G, P + PART_ZS, G, P + PART_RMAX, P + PART_SIG1, s->pcg_state, cr1,
-			                   (const int *)s->slot_l1, CoarseFields<real>{}, CoarseArgs{});
-		}
+		launch_pcg_b<real>(s, is_ml(s) && s->n_l1tiles <= 64, GB, (const real *)s->vs2, P + PART_SIG0, G, P + PART_ZS, G, P + PART_SIG1,
+		                   (real *)s->c_r, cr1);
 		break;
 	}
 	case LFA_K_MG_AXPY_PRESMOOTH: return lfa_mg_bench_part(s, 0);

@@ -124,6 +124,21 @@ def test_pcg_pressure_within_tolerance(name, precond, dtype):
     s.close()
 
 
+@pytest.mark.parametrize("dtype", [lfa.PCG_F32, lfa.PCG_F64])
+@pytest.mark.parametrize("precond", [lfa.PRECOND_MIC0_TILED, lfa.PRECOND_MULTILEVEL])
+@pytest.mark.parametrize("name", ["apic16_solid", "pic_ragged", "apic_h17"])
+def test_unfused_iteration_reaches_the_golden_pressure(name, precond, dtype):
+    """pcg_fused=0: the launch-per-operation iteration with the tile-local preconditioners (otherwise only the exact schedule takes it)."""
+    c, parts, solid, s = make_gpu(name, precond=precond, pcg_dtype=dtype, pcg_fused=0)
+    g = util.load_golden(name)
+    s.hash()
+    s.upload_cells(cells_from(g["grav_vel0"], g["p2g_type0"]))
+    p, res, it, rc = s.solve(util.DT)
+    assert rc == 0 and 0 < it <= 200 and res < 1e-6
+    util.assert_close(p, g["p0"], P_REL, "pressure")
+    s.close()
+
+
 @pytest.mark.parametrize("name", sorted(util.CASES))
 def test_apply_pressure_extrapolate_g2p(name):
     """Each downstream stage from the reference's state of the stage before it."""

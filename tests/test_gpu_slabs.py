@@ -99,12 +99,10 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("precond", [lfa.PRECOND_MIC0_TILED, lfa.PRECOND_MULTILEVEL])
-@pytest.mark.parametrize("size,block,method,bounds", CASES)
-def test_virtual_slabs_match_single_domain(size, block, method, bounds, precond):
+def check_slabs_match_single_domain(size, block, method, bounds, precond, **extra):
     solid = util.scenes.sphere_solid_cells(size, (size[0] / 2, 3, size[2] / 2), 2.6)
     solid = solid[(solid[:, 0] < block[0][0]) | (solid[:, 0] >= block[1][0]) | (solid[:, 1] >= block[1][1])]
-    kw = dict(precond=precond, pcg_dtype=lfa.PCG_F64)
+    kw = dict(precond=precond, pcg_dtype=lfa.PCG_F64, **extra)
     c1, p1, it1 = run_single(size, block, method, 2, solid=solid, **kw)
     cn, pn, itn = run_slabs(size, block, method, 2, bounds, solid=solid, **kw)
     assert len(pn) == len(p1)
@@ -118,6 +116,19 @@ def test_virtual_slabs_match_single_domain(size, block, method, bounds, precond)
     if precond == lfa.PRECOND_MIC0_TILED:
         # the tile-local preconditioner does not depend on the decomposition: same iteration counts
         assert itn[0] == it1
+
+
+@pytest.mark.parametrize("precond", [lfa.PRECOND_MIC0_TILED, lfa.PRECOND_MULTILEVEL])
+@pytest.mark.parametrize("size,block,method,bounds", CASES)
+def test_virtual_slabs_match_single_domain(size, block, method, bounds, precond):
+    check_slabs_match_single_domain(size, block, method, bounds, precond)
+
+
+@pytest.mark.parametrize("precond", [lfa.PRECOND_MIC0_TILED, lfa.PRECOND_MULTILEVEL])
+@pytest.mark.parametrize("size,block,method,bounds", [CASES[0], CASES[3]])
+def test_virtual_slabs_unfused_iteration_matches_single_domain(size, block, method, bounds, precond):
+    """pcg_fused=0 on slabs: two slabs, and fluid only in the lower one (the other rank has no particle tile)."""
+    check_slabs_match_single_domain(size, block, method, bounds, precond, pcg_fused=0)
 
 
 @pytest.mark.parametrize("faulty", [0, 1])
