@@ -210,21 +210,30 @@ __global__ void k_scatter_particles(MeshGrid g, const double *pos, size_t np, co
 /// The scatter leaves a cell's particles in arbitrary order; the reference visits them newest first, so each group is put
 /// in DESCENDING input order. Cells are x fastest, so the cells [x0, x1) of one row of a neighbourhood are one contiguous
 /// run of `order` that already is in the reference's visiting order (cells ascending, newest first inside a cell).
-/// Groups are a handful of particles: insertion sort, one thread per cell.
+/// Groups are a handful of particles: insertion sort, one thread per cell. A crowded cell (thousands of particles pressed into
+/// a corner) gets passes at wider gaps first (Shell sort, Ciura's gaps): the keys are distinct, so the order that comes out is
+/// the same, after n^1.3 instead of n^2 / 4 moves - 3 000 shuffled particles in one cell took 0.45 s. A group of up to 4 only
+/// sees the last pass, the insertion sort.
 /// `ids` (optional): the order key of particle i instead of i itself - a rank of a slab run holds its particles in storage
 /// order and orders them by their global ids, which is the single domain's input order.
 __global__ void k_sort_groups(const uint32_t *cell_start, size_t ncell, uint32_t *order, const uint32_t *ids) {
 	const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= ncell) return;
 	const uint32_t b = cell_start[c], e = cell_start[c + 1];
-	for (uint32_t i = b + 1; i < e; ++i) {
-		const uint32_t v = order[i];
-		uint32_t j = i;
-		while (j > b && (ids ? ids[order[j - 1]] < ids[v] : order[j - 1] < v)) {
-			order[j] = order[j - 1];
-			--j;
+	if (e - b < 2) return;
+	const uint32_t gaps[9] = {1750, 701, 301, 132, 57, 23, 10, 4, 1};
+	for (int g = 0; g < 9; ++g) {
+		const uint32_t gap = gaps[g];
+		if (gap >= e - b) continue;
+		for (uint32_t i = b + gap; i < e; ++i) {
+			const uint32_t v = order[i];
+			uint32_t j = i;
+			while (j >= b + gap && (ids ? ids[order[j - gap]] < ids[v] : order[j - gap] < v)) {
+				order[j] = order[j - gap];
+				j -= gap;
+			}
+			order[j] = v;
 		}
-		order[j] = v;
 	}
 }
 
