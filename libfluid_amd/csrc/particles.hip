@@ -305,7 +305,7 @@ __device__ inline float hash_unit(uint32_t a, uint32_t b, uint32_t k) {
 #define FB_ROWS (FB * FBZ)
 #define FINE_CAP 5632                       // staged particles (13 x 13 x 8 whole fine cells hold 4160 at 8 per cell)
 #define FINE_CAP_BIG 12288                   // the second pass over flagged parts: 144 KB of positions, one workgroup per CU
-// (own particles the u16 list of k_correct_fine holds: its count array, where it lives; more are found through the row offsets)
+// (own particles the u16 list of k_correct_fine holds: 3 072, in the second pass 4 096; more are found through the row offsets)
 #define FIDX_THREADS 512   // (256: 0.75 ms at C4, 512: 0.58; FIDX_STAGE and FIDX_CNT are multiples of it)
 #define FIDX_CNT (((FT3 + 1 + FIDX_THREADS - 1) / FIDX_THREADS) * FIDX_THREADS)  // index kernel: >= FT3 + 1, a multiple of FIDX_THREADS
 #define FIDX_STAGE 4608                      // records staged in LDS per tile by the index kernel (72 KB)
@@ -601,12 +601,12 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
                 const uint8_t *solid, const uint32_t *tile_count, const uint32_t *fine_start, const float4 *spos, MoveParams mp,
                 uint32_t *overflow_tiles, const uint8_t *tile_clear, const uint32_t *only) {
 	constexpr int T = ONLY ? CORR_THREADS_BIG : CORR_THREADS;  // threads of the workgroup
-	constexpr int CNT0 = ((FB_N + 1 + 2 * T - 1) / (2 * T)) * (2 * T);  // >= FB_N + 1, a multiple of 2 T
-	constexpr int CNT = ONLY && CNT0 < 4096 ? 4096 : CNT0;  // (the second pass has the room to list 4 096 own particles)
+	constexpr int CNT0 = ((FB_N + 1 + 2 * T - 1) / (2 * T)) * (2 * T);  // >= FB_N + 1, a multiple of 2 T: the cells take CNT / 2 T rounds
+	constexpr int CNT = ONLY && CNT0 < 4096 ? 4096 : CNT0;  // own particles listed (the second pass has the room for 4 096)
 	__shared__ float px[CAP], py[CAP], pz[CAP];
-	__shared__ uint32_t fcnt2[CNT / 2];     // particles per block fine cell (<= CAP), two cells per word; afterwards the own list
-	uint16_t *fcnt = (uint16_t *)fcnt2;
-	__shared__ uint16_t foff[FB_N + 1];        // first staged slot of every block fine cell
+	__shared__ uint16_t own[CNT];              // the own list: staged slots of the part's own particles, in fine-cell order
+	__shared__ uint32_t foff2[(FB_N + 2) / 2]; // first staged slot of every block fine cell + the end, two per word
+	const uint16_t *foff = (const uint16_t *)foff2;
 	// Per fine row of the block, everything the staging derives from the row alone: four words read as one 128-bit load,
 	// [0..2] source record of staged slot s in the row's three runs (x-1 tile, own x tile, x+1 tile) is base[seg] + s
 	// [3]    first slot of the own x run | first slot of the x+1 run << 16
@@ -619,9 +619,7 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 	__shared__ uint32_t ownoff[FT * FT_PL + 1];
 	__shared__ int srct[27];                   // the source tiles around the own one
 	__shared__ uint32_t wsum[T / 64];
-	uint16_t *own = fcnt;
-	static_assert(CNT > FB_N && CNT % (2 * T) == 0 && FBX % 2 == 0 && CAP < 32768 && CNT < 32768, "fcnt sizing");
-	constexpr int PER = CNT / T;
+	static_assert(CNT > FB_N && CNT % (2 * T) == 0 && FBX % 2 == 0 && CAP < 32768 && CNT < 32768, "own list and cell rounds sizing");
 	const int nn[3] = {g.nx, g.ny, g.nz};
 	const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 	if (ONLY && only[0] == 0) return;  // (as a rule)
@@ -629,7 +627,16 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 	// its own particles - the pair work of such a part is several times a normal one's, and there are fewer of them than CUs)
 	constexpr int SLICES = ONLY ? CORR_BIG_SLICES : 1;
 	for (int item = blockIdx.x; item < SLICES * CORR_PARTS * n_ptiles; item += gridDim.x) {
-		const int work = item / SLICES, slice = item % SLICES;
+		int work = item / SLICES;
+		const int slice = item % SLICES;
+		// (first pass: workgroups are handed to the eight XCDs in turn, and the parts of a tile write interleaved halves of the same
+		// lines of the outputs and stage two fine layers in common - so they are items 8 apart, on one XCD and one L2: of every
+		// 8 CORR_PARTS items the first eight are part 0 of eight tiles, the next eight their part 1. The tiles left over at the end
+		// keep item = work. The grid is a multiple of 8 or the whole of the items. Measured at C4: 4.19 -> 3.91 ms, the bytes
+		// written to HBM halved; four consecutive tiles with both parts per XCD instead: 3.96. docs/experiments.md, "cheaper block
+		// set-up".)
+		if (!ONLY && (item / (8 * CORR_PARTS)) * 8 + 8 <= n_ptiles)
+			work = CORR_PARTS * ((item / (8 * CORR_PARTS)) * 8 + item % 8) + (item % (8 * CORR_PARTS)) / 8;
 		if (ONLY && !((only[1 + (work >> 5)] >> (work & 31)) & 1u)) continue;  // (uniform)
 		const int tile = ptiles[work / CORR_PARTS], part = work % CORR_PARTS;
 		int tx, ty, tz;
@@ -660,54 +667,76 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			                        fy, fz);
 		}
 		__syncthreads();
+		// A source tile's index IS a prefix sum (fine_start), and a block row is three contiguous runs of it - two half cells of the
+		// x-1 tile, the own x tile's 22, two of the x+1 tile: the first staged slot of a block cell is fine_start[its source cell]
+		// minus the run's base (first source record - first slot, what the row descriptor holds anyway). Only the rows' three run
+		// lengths are scanned, by the rows' threads; nothing is counted per cell. (Before: a count per cell, scanned six per thread -
+		// 356 static VALU per work item.)
 		// (a thread takes two neighbouring half cells, bx even and bx + 1: they lie in the same source tile - the block's x halo is
-		// two half cells, the own run 22 - next to each other in its index: one look-up, three loads for two counts)
+		// two half cells, the own run 22 - next to each other in its index: one look-up, two loads. They are issued here, together
+		// with the rows' loads, and wait in registers for the bases)
 		constexpr int ROUNDS = CNT / (2 * T), KEPT = ROUNDS - 1 < 2 ? ROUNDS - 1 : 2;
+		uint32_t fs0[ROUNDS], fs1[ROUNDS];
+		int fbase[ROUNDS];  // the cell's run in rowd; -1: a cell behind the last row
 #pragma unroll
 		for (int k = 0; k < ROUNDS; ++k) {
 			// (all but the first KEPT rounds' cell coordinates are worked out per work item, not kept in registers across the loop: see `tid`)
 			const int p = (int)(k >= KEPT ? tid : threadIdx.x) + T * k;
-			uint32_t cnt0 = 0, cnt1 = 0, src0 = 0;
+			fs0[k] = 0; fs1[k] = 0; fbase[k] = -1;
 			if (p < (FBX / 2) * nrows) {
 				const int bx = 2 * (p % (FBX / 2)), row = p / (FBX / 2), by = row % FB, bz = row / FB;
 				const int gx = bx - 2, gy = by - 1, gz = gz0 + bz;
 				const int dx = gx < 0 ? 0 : (gx >= FTX ? 2 : 1), dy = gy < 0 ? 0 : (gy >= FT ? 2 : 1), dz = gz < 0 ? 0 : (gz >= FT ? 2 : 1);
 				const int src = srct[dx + 3 * dy + 9 * dz];
-				if (src >= 0) {
+				fbase[k] = row * 4 + dx;
+				if (src >= 0) {  // (a tile without particles: an empty run, whose base is minus its first slot)
 					const uint32_t fid = (uint32_t)((gx - FTX * (dx - 1)) + FTX * ((gy - FT * (dy - 1)) + FT * (gz - FT * (dz - 1))));
 					const uint32_t *fs = fine_start + ((uint32_t)src * FT_STRIDE + fid);  // (nt * FT_STRIDE < 2^32 up to 1.6 M tiles)
-					src0 = fs[0];
-					const uint32_t mid = fs[1];
-					cnt0 = mid - src0;
-					cnt1 = fs[2] - mid;  // (fid is even: fid + 2 <= FT3)
+					fs0[k] = fs[0]; fs1[k] = fs[1];
 				}
-				// the first cell of each of the row's three runs (biased by the run's first slot below)
-				if (bx == 0 || bx == 2 || bx == FBX - 2) rowd[row * 4 + (bx == 0 ? 0 : (bx == 2 ? 1 : 2))] = src0;
 			}
-			// (a cell of 2^16 - 1 alone exceeds CAP: the part is flagged below)
-			fcnt2[p] = (cnt0 < 0xFFFFu ? cnt0 : 0xFFFFu) | ((cnt1 < 0xFFFFu ? cnt1 : 0xFFFFu) << 16);
+		}
+		// ---- the rows: thread r has row r's three runs - first source record, length - and, for an own row (by = 1 .. FT,
+		// bz = 1 .. nzb - 2), the length of its middle run = its own particles. Two scans in one go over the first two waves: the
+		// rows' first slots and the own rows' first list entries (own rows come in list order).
+		static_assert(FB_ROWS <= 128 && T >= 256, "the rows are the first two waves; wsum holds two sums of each scan");
+		uint32_t run_at[3] = {0, 0, 0}, run_n[3] = {0, 0, 0}, row_incl = 0, own_incl = 0, row_n = 0, own_len = 0;
+		int own_row = -1;  // which own row this thread's row is
+		uint32_t rowe_lo = 0;
+		if (tid < 128u) {  // (whole waves: the shuffles need every lane)
+			const int r = (int)tid, by = r % FB, bz = r / FB;
+			const int gy = by - 1, gz = gz0 + bz;
+			const int dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0), dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
+			const int fy = gy - FT * dy, fz = gz - FT * dz;
+			if (r < nrows) {
+				const uint32_t frow = (uint32_t)(FTX * (fy + FT * fz));
+#pragma unroll
+				for (int seg = 0; seg < 3; ++seg) {
+					const int src = srct[seg + 3 * (dy + 1) + 9 * (dz + 1)];
+					if (src >= 0) {
+						const uint32_t *fs = fine_start + ((uint32_t)src * FT_STRIDE + frow + (seg == 0 ? FTX - 2 : 0));
+						run_at[seg] = fs[0];
+						run_n[seg] = fs[seg == 1 ? FTX : 2] - run_at[seg];  // (frow + FTX <= FT3: the entry behind the tile's last cell)
+					}
+				}
+				row_n = run_n[0] + run_n[1] + run_n[2];
+				if (by >= 1 && by <= FT && bz >= 1 && bz <= nzb - 2) {
+					own_row = (by - 1) + FT * (bz - 1);
+					own_len = run_n[1];
+				}
+				rowe_lo = (uint32_t)((8 * fy) / FT) | ((uint32_t)((8 * fz) / FT) << 3) | ((uint32_t)(8 * (dy + 1)) << 6) | ((uint32_t)(8 * (dz + 1)) << 11);
+			}
+			row_incl = row_n; own_incl = own_len;
+#pragma unroll
+			for (int o = 1; o < 64; o <<= 1) {
+				const uint32_t t = __shfl_up(row_incl, o, 64), u = __shfl_up(own_incl, o, 64);
+				if (lane >= o) { row_incl += t; own_incl += u; }
+			}
+			if (lane == 63) { wsum[wid] = row_incl; wsum[2 + wid] = own_incl; }
 		}
 		__syncthreads();
-		// ---- exclusive scan over the block's fine cells (thread t owns cells PER t .. PER t + PER - 1)
-		uint32_t c4[PER], sum = 0;
-#pragma unroll
-		for (int k = 0; k < PER; ++k) {
-			c4[k] = fcnt[PER * threadIdx.x + k];
-			sum += c4[k];
-		}
-		uint32_t incl = sum;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			uint32_t t = __shfl_up(incl, o, 64);
-			if (lane >= o) incl += t;
-		}
-		if (lane == 63) wsum[wid] = incl;
-		__syncthreads();
-		uint32_t woff = 0, total = 0;
-		for (int w = 0; w < T / 64; ++w) {
-			if (w < wid) woff += wsum[w];
-			total += wsum[w];
-		}
+		// (32-bit sums of disjoint record runs: no cell, however crowded, wraps them)
+		const uint32_t total = wsum[0] + wsum[1], own_total = wsum[2] + wsum[3];
 		if (total > (uint32_t)CAP) {  // uniform
 			if (threadIdx.x == 0 && slice == 0) {
 				atomicOr(&overflow_tiles[1 + (work >> 5)], 1u << (work & 31));
@@ -715,64 +744,32 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			}
 			continue;
 		}
-		{
-			uint32_t ex = woff + incl - sum;
-#pragma unroll
-			for (int k = 0; k < PER; ++k) {
-				const int f = PER * threadIdx.x + k;
-				if (f <= FB_N) foff[f] = (uint16_t)ex;
-				ex += c4[k];
-			}
-		}
-		__syncthreads();
-		// ---- own particles: the middle runs of the rows by = 1 .. FT, bz = 1 .. nzb - 2; their lengths, scanned by the first waves
-		uint32_t own_total = 0, own_first = 0;  // own_first: list entry of the first own particle of this thread's own row
-		{
-			uint32_t len = 0;
-			if (tid < (unsigned)nown_rows) {
-				const int row = (1 + (int)tid % FT) + FB * (1 + (int)tid / FT);
-				len = (uint32_t)foff[row * FBX + FBX - 2] - (uint32_t)foff[row * FBX + 2];
-			}
-			uint32_t in2 = len;
-#pragma unroll
-			for (int o = 1; o < 64; o <<= 1) {
-				uint32_t t = __shfl_up(in2, o, 64);
-				if (lane >= o) in2 += t;
-			}
-			if (lane == 63) wsum[wid] = in2;
-			__syncthreads();
-			uint32_t wo = 0;
-			for (int w = 0; w < T / 64; ++w) {
-				if (w < wid) wo += wsum[w];
-				own_total += wsum[w];
-			}
-			own_first = wo + in2 - len;
-			if (tid < (unsigned)nown_rows) ownoff[tid] = own_first;
-			if (tid == 0) ownoff[nown_rows] = own_total;
-		}
-		// (a crowded part with more own particles than the list holds - it lives in the count array - finds them through the row
-		// offsets instead: uniform)
+		// (a crowded part with more own particles than the list holds finds them through the row offsets instead: uniform)
 		const bool listed = own_total <= (uint32_t)CNT;
-		// ---- the row descriptors: thread r writes row r's, thread t the own-list base of the t-th own row (the top half of the
-		// packed word: two threads share the word, so the second one writes after a barrier)
+		// ---- the row descriptors, and the own rows' first list entries
 		if (tid < (unsigned)nrows) {
-			const int r = (int)tid, by = r % FB, bz = r / FB;
-			const int gy = by - 1, gz = gz0 + bz;
-			const int dy = gy < 0 ? -1 : (gy >= FT ? 1 : 0), dz = gz < 0 ? -1 : (gz >= FT ? 1 : 0);
-			const int fy = gy - FT * dy, fz = gz - FT * dz;
-			const uint32_t d0 = foff[r * FBX], d1 = foff[r * FBX + 2], d2 = foff[r * FBX + FBX - 2];
-			uint32_t *rd = rowd + r * 4;
-			rd[0] -= d0; rd[1] -= d1; rd[2] -= d2;
-			rd[3] = d1 | (d2 << 16);
-			rowe[r] = (uint32_t)((8 * fy) / FT) | ((uint32_t)((8 * fz) / FT) << 3) | ((uint32_t)(8 * (dy + 1)) << 6) |
-			          ((uint32_t)(8 * (dz + 1)) << 11) | ((uint32_t)ROW_NOT_OWN << 16);
+			const uint32_t d0 = (wid ? wsum[0] : 0u) + row_incl - row_n, d1 = d0 + run_n[0], d2 = d1 + run_n[1];
+			*(uint4 *)(rowd + tid * 4) = make_uint4(run_at[0] - d0, run_at[1] - d1, run_at[2] - d2, d1 | (d2 << 16));
+			uint32_t ob = (uint32_t)ROW_NOT_OWN;
+			if (own_row >= 0) {
+				const uint32_t own_first = (wid ? wsum[2] : 0u) + own_incl - own_len;  // list entry of the row's first own particle
+				ownoff[own_row] = own_first;
+				if (listed) ob = own_first - d1;
+			}
+			rowe[tid] = rowe_lo | (ob << 16);
+		}
+		if (tid == 0) ownoff[nown_rows] = own_total;
+		__syncthreads();
+		// ---- first staged slot of every block fine cell; the cells behind the last row, and the entry behind the last cell: `total`
+#pragma unroll
+		for (int k = 0; k < ROUNDS; ++k) {
+			const int p = (int)(k >= KEPT ? tid : threadIdx.x) + T * k;
+			if (p < (FB_N + 2) / 2) {
+				const uint32_t base = fbase[k] >= 0 ? rowd[fbase[k]] : 0u - total;
+				foff2[p] = ((fs0[k] - base) & 0xFFFFu) | ((fs1[k] - base) << 16);
+			}
 		}
 		__syncthreads();
-		if (listed && tid < (unsigned)nown_rows) {
-			const int row = (1 + (int)tid % FT) + FB * (1 + (int)tid / FT);
-			rowe[row] = (rowe[row] & 0xFFFFu) | ((own_first - (uint32_t)foff[row * FBX + 2]) << 16);
-		}
-		__syncthreads();  // (every count has been read: `own` may overwrite the array)
 		CORR_STAMP(0);  // counts, scans, own offsets
 		// ---- stage the rows: their three runs - two half cells of the x-1 tile, the own x tile's 22, two of the x+1 tile - follow
 		// each other in the block (positions relative to the own tile's origin, in cells)
