@@ -470,8 +470,6 @@ struct MemAgent {
 	template <typename T> static __device__ inline T ld(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 	template <typename T> static __device__ inline void st(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
-/// One colour of the Gauss-Seidel update on the column of a lane: x_i = (b_i + sum of coupled neighbours) / diag_i.
-/// `h` is the 10^3 halo block of the wave (current values, ring = values of the neighbour tiles or 0).
 /// What one Gauss-Seidel update needs of a cell's A byte: the couplings as 0 / 1 factors and the over-relaxed update
 ///   x <- x + omega (sum / diag - x)  =  (1 - omega) x + (omega / diag) sum
 /// as two coefficients. A cell that is no unknown (or has no non-solid neighbour) gets (keep, gain) = (1, 0): the update leaves
@@ -515,14 +513,14 @@ __device__ inline void gs_colour(real *h, const uint32_t (&ab)[8], const real (&
 		// (a select written as arithmetic: `z0 ? ab[2j+1] : ab[2j]` is turned into a dynamically indexed load from scratch)
 		const uint32_t a = ab[2 * j] ^ ((ab[2 * j] ^ ab[2 * j + 1]) & zmask);
 		const real bv = bit_select(bb[2 * j], bb[2 * j + 1], z0);
-		const int i = (lx + 1) + 10 * (ly + 1) + 100 * (2 * j + z0 + 1);
+		const int i = halo_at(lx, ly, 2 * j + z0);
 		// (the compiler keeps the decoded coefficients of all eight cells in registers across the sweeps: 3 waves per SIMD for the
 		// finest-level kernels; decoding per update instead - an opaque `asm` on `a` - measured no better, docs/experiments.md)
 		out[j] = gs_update<real>(gs_coef<real>(a), bv, h[i - 1], h[i - 10], h[i - 100], h[i + 1], h[i + 10], h[i + 100], h[i]);
 	}
 	// (cells of one colour do not read each other: the four results are stored behind all the reads)
 #pragma unroll
-	for (int j = 0; j < 4; ++j) h[(lx + 1) + 10 * (ly + 1) + 100 * (2 * j + z0 + 1)] = out[j];
+	for (int j = 0; j < 4; ++j) h[halo_at(lx, ly, 2 * j + z0)] = out[j];
 }
 
 /// Down, one tile: x = one red->black sweep on A x = b from x = 0 (`h`: ring already zero). With a zero guess the values
@@ -531,7 +529,7 @@ template <typename real>
 __device__ inline void presmooth_column(real *h, const uint32_t (&ab)[8], const real (&bb)[8], int lx, int ly, int inner) {
 	MG_FENCE();
 #pragma unroll
-	for (int zz = 0; zz < 8; ++zz) h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = (real)0;
+	for (int zz = 0; zz < 8; ++zz) h[halo_at(lx, ly, zz)] = (real)0;
 	MG_FENCE();
 	for (int it = 0; it < inner; ++it) {
 		gs_colour<real>(h, ab, bb, lx, ly, 0);
@@ -555,27 +553,55 @@ __device__ inline void presmooth_tile(const MgLv<real> &L, int slot, real *h, in
 	}
 	presmooth_column<real>(h, ab, bb, lx, ly, inner);
 #pragma unroll
-	for (int zz = 0; zz < 8; ++zz) ST::st(L.x + base + zz * 64 + lane, h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)]);
+	for (int zz = 0; zz < 8; ++zz) ST::st(L.x + base + zz * 64 + lane, h[halo_at(lx, ly, zz)]);
 }
 
-/// Halo block of a tile-major vector (k_spmv's layout): interior + the six faces of the neighbour tiles (0 if inactive).
-template <typename real, typename LD = MemPlain>
-__device__ inline void load_halo(real *h, const real *v, size_t base, const int *nb, int lane, int lx, int ly) {
+/// Where a tile restricts to: its parent tile (grid gc) and the offset of its octant in the parent's 512 cells.
+struct MgOctant {
+	int ptile, off;
+};
+__device__ inline MgOctant mg_octant(const GridDims &g, const GridDims &gc, int tile) {
+	int tx, ty, tz;
+	tile_coords(g, tile, tx, ty, tz);
+	return {(tx >> 1) + gc.ntx * ((ty >> 1) + gc.nty * (tz >> 1)), (tz & 1) * 256 + (ty & 1) * 32 + (tx & 1) * 4};
+}
+/// Restriction, wave form: the residuals of the lane's column (halo block `h`: iterate and ring) and half the sum over the 8
+/// children of a coarse cell - pair sums along z, then two shuffle steps along x and y. put(o, v): coarse value v for cell o of
+/// the tile's octant (lanes with even lx and ly, four cells each).
+template <typename real, typename Put>
+__device__ inline void restrict_column(const real *h, const uint32_t (&ab)[8], const real (&bb)[8], int lx, int ly, Put put) {
+	real pair[4];
 #pragma unroll
-	for (int zz = 0; zz < 8; ++zz) h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = LD::ld(v + base + zz * 64 + lane);
-	h[0 + 10 * (lx + 1) + 100 * (ly + 1)] = nb[0] >= 0 ? LD::ld(v + (size_t)nb[0] * 512 + ly * 64 + lx * 8 + 7) : (real)0;
-	h[9 + 10 * (lx + 1) + 100 * (ly + 1)] = nb[1] >= 0 ? LD::ld(v + (size_t)nb[1] * 512 + ly * 64 + lx * 8 + 0) : (real)0;
-	h[(lx + 1) + 10 * 0 + 100 * (ly + 1)] = nb[2] >= 0 ? LD::ld(v + (size_t)nb[2] * 512 + ly * 64 + 7 * 8 + lx) : (real)0;
-	h[(lx + 1) + 10 * 9 + 100 * (ly + 1)] = nb[3] >= 0 ? LD::ld(v + (size_t)nb[3] * 512 + ly * 64 + 0 * 8 + lx) : (real)0;
-	h[(lx + 1) + 10 * (ly + 1) + 100 * 0] = nb[4] >= 0 ? LD::ld(v + (size_t)nb[4] * 512 + 7 * 64 + lane) : (real)0;
-	h[(lx + 1) + 10 * (ly + 1) + 100 * 9] = nb[5] >= 0 ? LD::ld(v + (size_t)nb[5] * 512 + 0 * 64 + lane) : (real)0;
+	for (int zz = 0; zz < 8; ++zz) {
+		const real r = residual_cell<real>(h, ab[zz], bb[zz], halo_at(lx, ly, zz));
+		if (zz & 1) pair[zz >> 1] += r;
+		else pair[zz >> 1] = r;
+	}
+#pragma unroll
+	for (int j = 0; j < 4; ++j) {
+		real t = pair[j];
+		t += __shfl_xor(t, 1, 64);
+		t += __shfl_xor(t, 8, 64);
+		if (!(lx & 1) && !(ly & 1)) put(j * 64 + (ly >> 1) * 8 + (lx >> 1), (real)0.5 * t);
+	}
+}
+/// Restriction, LDS form: thread t < 64 sums the 8 children of ONE coarse cell from the tile's residuals R[512] in the order of
+/// restrict_column (the pair sums, the x step, the y step). Returns the coarse value, `o` = its cell in the tile's octant.
+template <typename real> __device__ inline real restrict_cell(const real *R, int t, int &o) {
+	const int X = t & 3, Y = (t >> 2) & 3, Z = t >> 4;
+	auto pair = [&](int x, int y) { real p = R[x + 8 * y + 64 * (2 * Z)]; p += R[x + 8 * y + 64 * (2 * Z + 1)]; return p; };
+	real v = pair(2 * X, 2 * Y);
+	v += pair(2 * X + 1, 2 * Y);
+	real w = pair(2 * X, 2 * Y + 1);
+	w += pair(2 * X + 1, 2 * Y + 1);
+	v += w;
+	o = Z * 64 + Y * 8 + X;
+	return (real)0.5 * v;
 }
 
 /// Down, one tile: residual r = b - A x of the level and its restriction to the next: half the sum over the 8 children.
-/// (`lds_parent`: the restricted values go to the parent tile's 512-entry block in LDS instead - k_mg_restrict0_pre1)
 template <typename real, typename LD = MemPlain, typename ST = MemPlain>
-__device__ inline void residual_restrict_tile(const MgLv<real> &L, const GridDims &gc, real *b_coarse, int slot, real *h, int lane,
-                                              real *lds_parent = nullptr) {
+__device__ inline void residual_restrict_tile(const MgLv<real> &L, const GridDims &gc, real *b_coarse, int slot, real *h, int lane) {
 	const int lx = lane & 7, ly = lane >> 3;
 	const int *nt = L.nbr + (size_t)slot * MG_NBR_STRIDE;
 	const int nb[6] = {nt[0], nt[1], nt[2], nt[3], nt[4], nt[5]}, tile = nt[6];
@@ -590,42 +616,11 @@ __device__ inline void residual_restrict_tile(const MgLv<real> &L, const GridDim
 		bb[zz] = LD::ld(L.b + base + zz * 64 + lane);
 	}
 	MG_FENCE();
-	load_halo<real, LD>(h, L.x, base, nb, lane, lx, ly);
+	load_halo<real>(h, [&](size_t j) { return LD::ld(L.x + j); }, base, nb, lane, lx, ly);
 	MG_FENCE();
-	real pair[4];
-#pragma unroll
-	for (int zz = 0; zz < 8; ++zz) {
-		const int i = (lx + 1) + 10 * (ly + 1) + 100 * (zz + 1);
-		const uint32_t a = ab[zz];
-		real r = (real)0;
-		if (a & AB_UNKNOWN) {
-			const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-			real val = (real)(a & 7) * h[i];
-			val = madd01(-F, h[i - 1], val);
-			val = madd01(-F, h[i - 10], val);
-			val = madd01(-F, h[i - 100], val);
-			val = madd01(-(real)((a >> 3) & 1), h[i + 1], val);
-			val = madd01(-(real)((a >> 4) & 1), h[i + 10], val);
-			val = madd01(-(real)((a >> 5) & 1), h[i + 100], val);
-			r = bb[zz] - val;
-		}
-		if (zz & 1) pair[zz >> 1] += r;
-		else pair[zz >> 1] = r;
-	}
-	int tx, ty, tz;
-	tile_coords(L.g, tile, tx, ty, tz);
-	const int ptile = (tx >> 1) + gc.ntx * ((ty >> 1) + gc.nty * (tz >> 1));
-#pragma unroll
-	for (int j = 0; j < 4; ++j) {
-		real t = pair[j];
-		t += __shfl_xor(t, 1, 64);
-		t += __shfl_xor(t, 8, 64);
-		if (!(lx & 1) && !(ly & 1)) {
-			const int o = ((tz & 1) * 4 + j) * 64 + ((ty & 1) * 4 + (ly >> 1)) * 8 + (tx & 1) * 4 + (lx >> 1);
-			if (lds_parent) lds_parent[o] = (real)0.5 * t;
-			else ST::st(b_coarse + (size_t)ptile * 512 + o, (real)0.5 * t);
-		}
-	}
+	const MgOctant oc = mg_octant(L.g, gc, tile);
+	real *out = b_coarse + (size_t)oc.ptile * 512 + oc.off;
+	restrict_column<real>(h, ab, bb, lx, ly, [&](int o, real v) { ST::st(out + o, v); });
 }
 
 /// Up, one tile: x += P e (piecewise constant prolongation of the next level's solution), then one black->red sweep with
@@ -649,7 +644,7 @@ __device__ inline void prolong_postsmooth_tile(const MgLv<real> &L, const GridDi
 		bb[zz] = L.b[base + zz * 64 + lane];
 		real v = L.x[base + zz * 64 + lane];
 		if (ab[zz] & AB_UNKNOWN) v += corr(tx * 8 + lx, ty * 8 + ly, tz * 8 + zz);
-		h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = v;
+		h[halo_at(lx, ly, zz)] = v;
 	}
 	// ring: face lanes = (a, b) over the two in-face axes; a ring cell is corrected like its own tile corrects it
 	auto ring = [&](int nbk, int cell, int X, int Y, int Z) -> real {
@@ -659,12 +654,13 @@ __device__ inline void prolong_postsmooth_tile(const MgLv<real> &L, const GridDi
 		if (L.abits[j] & AB_UNKNOWN) v += corr(X, Y, Z);
 		return v;
 	};
-	h[0 + 10 * (lx + 1) + 100 * (ly + 1)] = ring(nb[0], ly * 64 + lx * 8 + 7, tx * 8 - 1, ty * 8 + lx, tz * 8 + ly);
-	h[9 + 10 * (lx + 1) + 100 * (ly + 1)] = ring(nb[1], ly * 64 + lx * 8 + 0, tx * 8 + 8, ty * 8 + lx, tz * 8 + ly);
-	h[(lx + 1) + 10 * 0 + 100 * (ly + 1)] = ring(nb[2], ly * 64 + 7 * 8 + lx, tx * 8 + lx, ty * 8 - 1, tz * 8 + ly);
-	h[(lx + 1) + 10 * 9 + 100 * (ly + 1)] = ring(nb[3], ly * 64 + 0 * 8 + lx, tx * 8 + lx, ty * 8 + 8, tz * 8 + ly);
-	h[(lx + 1) + 10 * (ly + 1) + 100 * 0] = ring(nb[4], 7 * 64 + lane, tx * 8 + lx, ty * 8 + ly, tz * 8 - 1);
-	h[(lx + 1) + 10 * (ly + 1) + 100 * 9] = ring(nb[5], 0 * 64 + lane, tx * 8 + lx, ty * 8 + ly, tz * 8 + 8);
+	const real fv[6] = {ring(nb[0], ly * 64 + lx * 8 + 7, tx * 8 - 1, ty * 8 + lx, tz * 8 + ly),
+	                    ring(nb[1], ly * 64 + lx * 8 + 0, tx * 8 + 8, ty * 8 + lx, tz * 8 + ly),
+	                    ring(nb[2], ly * 64 + 7 * 8 + lx, tx * 8 + lx, ty * 8 - 1, tz * 8 + ly),
+	                    ring(nb[3], ly * 64 + 0 * 8 + lx, tx * 8 + lx, ty * 8 + 8, tz * 8 + ly),
+	                    ring(nb[4], 7 * 64 + lane, tx * 8 + lx, ty * 8 + ly, tz * 8 - 1),
+	                    ring(nb[5], 0 * 64 + lane, tx * 8 + lx, ty * 8 + ly, tz * 8 + 8)};
+	store_halo_faces(h, lx, ly, fv);
 	MG_FENCE();
 	for (int it = 0; it < inner; ++it) {
 		gs_colour<real>(h, ab, bb, lx, ly, 1);
@@ -686,7 +682,7 @@ template <typename real> __device__ inline void coarsest_tile(const MgLv<real> &
 	for (int zz = 0; zz < 8; ++zz) {
 		ab[zz] = L.abits[base + zz * 64 + lane];
 		bb[zz] = L.b[base + zz * 64 + lane];
-		h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = (real)0;
+		h[halo_at(lx, ly, zz)] = (real)0;
 	}
 	MG_FENCE();
 	for (int k = 0; k < 2 * nsw; ++k) {
@@ -697,7 +693,7 @@ template <typename real> __device__ inline void coarsest_tile(const MgLv<real> &
 		MG_FENCE();
 	}
 #pragma unroll
-	for (int zz = 0; zz < 8; ++zz) L.y[base + zz * 64 + lane] = h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)];
+	for (int zz = 0; zz < 8; ++zz) L.y[base + zz * 64 + lane] = h[halo_at(lx, ly, zz)];
 }
 
 template <typename real>
@@ -778,7 +774,7 @@ k_mg_axpy_presmooth(const int *tiles, int n_tiles, const uint8_t *abits, real *p
 			if (slot < n_tiles) load_tile(__builtin_amdgcn_readlane(ids, turn));
 			presmooth_column<real>(h, ab, bb, lx, ly, MG_INNER_SWEEPS);
 #pragma unroll
-			for (int zz = 0; zz < 8; ++zz) q_x[obase + zz * 64 + lane] = h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)];
+			for (int zz = 0; zz < 8; ++zz) q_x[obase + zz * 64 + lane] = h[halo_at(lx, ly, zz)];
 		}
 	}
 	m = wave_max(m);
@@ -788,7 +784,7 @@ k_mg_axpy_presmooth(const int *tiles, int n_tiles, const uint8_t *abits, real *p
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		double v = lds[8];
-		for (int i = 1; i < 4; ++i) v = (v != v || lds[8 + i] != lds[8 + i]) ? NAN : (lds[8 + i] > v ? lds[8 + i] : v);
+		for (int i = 1; i < 4; ++i) v = nan_max(v, lds[8 + i]);
 		part_rmax[blockIdx.x] = v;
 	}
 }
@@ -814,16 +810,9 @@ k_mg_axpy_presmooth_cg(const int *tiles, int n_tiles, const uint8_t *abits, real
 	bool run = state[0] < 0;
 	if (run && iter > 0) {  // every workgroup evaluates the rule on the same values, workgroup 0 records it
 		double rm = rmax_prev[0];
-		for (int i = 1; i < n_rmax; ++i) rm = (rm != rm || rmax_prev[i] != rmax_prev[i]) ? NAN : (rmax_prev[i] > rm ? rmax_prev[i] : rm);
-		const bool stop = rm != rm || rm < tol;
-		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			hist[iter - 1] = rm;
-			if (stop) {
-				if (rm != rm) state[1] = 1;
-				*(double *)(state + 16) = rm;
-				state[0] = iter;
-			}
-		}
+		for (int i = 1; i < n_rmax; ++i) rm = nan_max(rm, rmax_prev[i]);
+		const bool stop = verdict_stops(rm, tol);
+		if (blockIdx.x == 0 && threadIdx.x == 0) record_verdict(state, hist, iter - 1, rm, stop);
 		run = !stop;
 	}
 	if (run) {
@@ -883,7 +872,7 @@ k_mg_axpy_presmooth_cg(const int *tiles, int n_tiles, const uint8_t *abits, real
 			if (slot < n_tiles) load_tile(slot);
 			presmooth_column<real>(h, ab, bb, lx, ly, MG_INNER_SWEEPS);
 #pragma unroll
-			for (int zz = 0; zz < 8; ++zz) w_x[obase + zz * 64 + lane] = h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)];
+			for (int zz = 0; zz < 8; ++zz) w_x[obase + zz * 64 + lane] = h[halo_at(lx, ly, zz)];
 		}
 	}
 	m = wave_max(m);
@@ -893,7 +882,7 @@ k_mg_axpy_presmooth_cg(const int *tiles, int n_tiles, const uint8_t *abits, real
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		double v = lds[0];
-		for (int i = 1; i < 4; ++i) v = (v != v || lds[i] != lds[i]) ? NAN : (lds[i] > v ? lds[i] : v);
+		for (int i = 1; i < 4; ++i) v = nan_max(v, lds[i]);
 		part_rmax[blockIdx.x] = v;
 	}
 }
@@ -957,16 +946,9 @@ __global__ void __launch_bounds__(256) k_mg_residual_restrict(MgLv<real> L, Grid
 		if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nan ? NAN : a;
 		__syncthreads();
 		double rmax = red[0];
-		for (int k = 1; k < 4; ++k) rmax = (rmax != rmax || red[k] != red[k]) ? NAN : (red[k] > rmax ? red[k] : rmax);
-		const bool done = rmax != rmax || rmax < stop.tol;
-		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			stop.hist[stop.iter] = rmax;
-			if (done) {
-				if (rmax != rmax) stop.state[1] = 1;
-				*(double *)(stop.state + 16) = rmax;
-				stop.state[0] = stop.iter + 1;
-			}
-		}
+		for (int k = 1; k < 4; ++k) rmax = nan_max(rmax, red[k]);
+		const bool done = verdict_stops(rmax, stop.tol);
+		if (blockIdx.x == 0 && threadIdx.x == 0) record_verdict(stop.state, stop.hist, stop.iter, rmax, done);
 		if (done) return;
 	}
 	// residual_restrict_tile as a software pipeline with branch-free loads (k_mg_prolong_postsmooth): the table row a tile ahead,
@@ -980,14 +962,12 @@ __global__ void __launch_bounds__(256) k_mg_residual_restrict(MgLv<real> L, Grid
 		for (int zz = 0; zz < 8; ++zz) {
 			ab[zz] = tab[zz];
 			bb[zz] = tb[zz];
-			h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = tx[zz];
+			h[halo_at(lx, ly, zz)] = tx[zz];
 		}
-		h[0 + 10 * (lx + 1) + 100 * (ly + 1)] = rv[0] ? rx[0] : (real)0;
-		h[9 + 10 * (lx + 1) + 100 * (ly + 1)] = rv[1] ? rx[1] : (real)0;
-		h[(lx + 1) + 10 * 0 + 100 * (ly + 1)] = rv[2] ? rx[2] : (real)0;
-		h[(lx + 1) + 10 * 9 + 100 * (ly + 1)] = rv[3] ? rx[3] : (real)0;
-		h[(lx + 1) + 10 * (ly + 1) + 100 * 0] = rv[4] ? rx[4] : (real)0;
-		h[(lx + 1) + 10 * (ly + 1) + 100 * 9] = rv[5] ? rx[5] : (real)0;
+		real fv[6];
+#pragma unroll
+		for (int k = 0; k < 6; ++k) fv[k] = rv[k] ? rx[k] : (real)0;
+		store_halo_faces(h, lx, ly, fv);
 		slot += stride;
 		{
 			const int crow = nrow;
@@ -995,39 +975,9 @@ __global__ void __launch_bounds__(256) k_mg_residual_restrict(MgLv<real> L, Grid
 			if (slot < L.n_tiles) load_tile(crow);
 		}
 		MG_FENCE();
-		real pair[4];
-#pragma unroll
-		for (int zz = 0; zz < 8; ++zz) {
-			const int i = (lx + 1) + 10 * (ly + 1) + 100 * (zz + 1);
-			const uint32_t a = ab[zz];
-			real r = (real)0;
-			if (a & AB_UNKNOWN) {
-				const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-				real val = (real)(a & 7) * h[i];
-				val = madd01(-F, h[i - 1], val);
-				val = madd01(-F, h[i - 10], val);
-				val = madd01(-F, h[i - 100], val);
-				val = madd01(-(real)((a >> 3) & 1), h[i + 1], val);
-				val = madd01(-(real)((a >> 4) & 1), h[i + 10], val);
-				val = madd01(-(real)((a >> 5) & 1), h[i + 100], val);
-				r = bb[zz] - val;
-			}
-			if (zz & 1) pair[zz >> 1] += r;
-			else pair[zz >> 1] = r;
-		}
-		int tx_, ty_, tz_;
-		tile_coords(L.g, tile, tx_, ty_, tz_);
-		const int ptile = (tx_ >> 1) + gc.ntx * ((ty_ >> 1) + gc.nty * (tz_ >> 1));
-#pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			real t = pair[j];
-			t += __shfl_xor(t, 1, 64);
-			t += __shfl_xor(t, 8, 64);
-			if (!(lx & 1) && !(ly & 1)) {
-				const int o = ((tz_ & 1) * 4 + j) * 64 + ((ty_ & 1) * 4 + (ly >> 1)) * 8 + (tx_ & 1) * 4 + (lx >> 1);
-				b_coarse[(size_t)ptile * 512 + o] = (real)0.5 * t;
-			}
-		}
+		const MgOctant oc = mg_octant(L.g, gc, tile);
+		real *out = b_coarse + (size_t)oc.ptile * 512 + oc.off;
+		restrict_column<real>(h, ab, bb, lx, ly, [&](int o, real v) { out[o] = v; });
 	}
 }
 
@@ -1111,7 +1061,7 @@ k_mg_prolong_postsmooth(MgLv<real> L, GridDims gc, const real *e, real inv_scale
 				bb[zz] = tb[zz];
 				real v = tx[zz];
 				if (ab[zz] & AB_UNKNOWN) v += tc[zz >> 1];
-				h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = v;
+				h[halo_at(lx, ly, zz)] = v;
 			}
 			real fv[6];
 #pragma unroll
@@ -1120,12 +1070,7 @@ k_mg_prolong_postsmooth(MgLv<real> L, GridDims gc, const real *e, real inv_scale
 				if (rab[k] & AB_UNKNOWN) v += rc[k];
 				fv[k] = rv[k] ? v : (real)0;
 			}
-			h[0 + 10 * (lx + 1) + 100 * (ly + 1)] = fv[0];
-			h[9 + 10 * (lx + 1) + 100 * (ly + 1)] = fv[1];
-			h[(lx + 1) + 10 * 0 + 100 * (ly + 1)] = fv[2];
-			h[(lx + 1) + 10 * 9 + 100 * (ly + 1)] = fv[3];
-			h[(lx + 1) + 10 * (ly + 1) + 100 * 0] = fv[4];
-			h[(lx + 1) + 10 * (ly + 1) + 100 * 9] = fv[5];
+			store_halo_faces(h, lx, ly, fv);
 			slot += stride;
 			{
 				const int crow = nrow;  // (the row of the next tile: here since the last iteration)
@@ -1141,7 +1086,7 @@ k_mg_prolong_postsmooth(MgLv<real> L, GridDims gc, const real *e, real inv_scale
 			}
 #pragma unroll
 			for (int zz = 0; zz < 8; ++zz) {
-				const real v = h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)];
+				const real v = h[halo_at(lx, ly, zz)];
 				if (LEVEL0) {
 					const real zv = v * inv_scale;
 					L.y[obase + zz * 64 + lane] = zv;
@@ -1169,34 +1114,62 @@ template <typename real> __device__ inline void gs_cell(real *H, uint32_t a, rea
 // kernel of theirs is a handful of waves, each alone on its SIMD, waiting out the latency of ~140 dependent instructions per
 // half sweep (s_memtime: 2300 cycles). Here a WORKGROUP takes a tile: a thread per cell of a colour in the half sweeps, two
 // cells per thread elsewhere, a barrier between the steps. Same operations in the same order per cell: bit-identical to
-// k_mg_presmooth / k_mg_residual_restrict / k_mg_prolong_postsmooth (LFA_MG_NO_CP=1 selects those; tested).
+// k_mg_presmooth / k_mg_residual_restrict / k_mg_prolong_postsmooth (which levels of more than 1024 tiles keep, MgPlan::Level::cp; tested).
 template <typename real> struct CpTile {
 	real H[LFA_HALO_CELLS];
 	real bb[512];
 	uint8_t ab[512];
 };
+/// One half sweep as a workgroup: thread t (0 .. 255) updates its cell of colour `colour`, column (t & 7, (t >> 3) & 7).
+template <typename real> __device__ inline void gs_half_sweep(real *H, const uint8_t *ab, const real *bb, int t, int colour) {
+	const int qx = t & 7, qy = (t >> 3) & 7, z = 2 * (t >> 6) + ((qx + qy + colour) & 1), c = qx + 8 * qy + 64 * z;
+	gs_cell<real>(H, ab[c], bb[c], halo_at(qx, qy, z));
+}
 template <typename real> __device__ inline void cp_half_sweep(CpTile<real> &S, int colour) {
-	const int t = threadIdx.x, qx = t & 7, qy = (t >> 3) & 7, z = 2 * (t >> 6) + ((qx + qy + colour) & 1), c = qx + 8 * qy + 64 * z;
-	gs_cell<real>(S.H, S.ab[c], S.bb[c], (qx + 1) + 10 * (qy + 1) + 100 * (z + 1));
+	gs_half_sweep<real>(S.H, S.ab, S.bb, threadIdx.x, colour);
 	__syncthreads();
 }
-__device__ inline int cp_hi(int cell) { return ((cell & 7) + 1) + 10 * (((cell >> 3) & 7) + 1) + 100 * ((cell >> 6) + 1); }
+__device__ inline int cp_hi(int cell) { return halo_at(cell & 7, (cell >> 3) & 7, cell >> 6); }
 
-/// Down, one tile, a workgroup of 256: x = `inner` red->black sweeps on A x = b from x = 0.
-template <typename real, typename MEM> __device__ inline void cp_presmooth_tile(CpTile<real> &S, const MgLv<real> &L, int slot, int inner) {
-	const int t = threadIdx.x;
-	const size_t base = (size_t)L.tiles[slot] * 512;
-	for (int c = t; c < 512; c += 256) {
+// Each phase is load, compute, store: k_mg_coarse's launch-order form (top_*) moves the values as tagged words and runs the same compute.
+/// Load: A bytes and right-hand side of the tile at `base`.
+template <typename real, typename MEM> __device__ inline void cp_load_system(CpTile<real> &S, const MgLv<real> &L, size_t base) {
+	for (int c = threadIdx.x; c < 512; c += 256) {
 		S.ab[c] = L.abits[base + c];
 		S.bb[c] = MEM::ld(L.b + base + c);
 	}
-	for (int i = t; i < LFA_HALO_CELLS; i += 256) S.H[i] = (real)0;
-	__syncthreads();
-	for (int it = 0; it < inner; ++it) {
-		cp_half_sweep<real>(S, 0);
-		cp_half_sweep<real>(S, 1);
+}
+/// Compute: n sweeps, each `first` then the other colour.
+template <typename real> __device__ inline void cp_sweeps(CpTile<real> &S, int n, int first) {
+	for (int it = 0; it < n; ++it) {
+		cp_half_sweep<real>(S, first);
+		cp_half_sweep<real>(S, first ^ 1);
 	}
-	for (int c = t; c < 512; c += 256) MEM::st(L.x + base + c, S.H[cp_hi(c)]);
+}
+/// Compute: `inner` red->black sweeps from x = 0 (the ring does not enter: the whole block is zeroed).
+template <typename real> __device__ inline void cp_presmooth(CpTile<real> &S, int inner) {
+	for (int i = threadIdx.x; i < LFA_HALO_CELLS; i += 256) S.H[i] = (real)0;
+	__syncthreads();
+	cp_sweeps<real>(S, inner, 0);
+}
+/// Compute: residuals of the tile into R[512], then their restriction; put(o, v): coarse value v for cell o of the tile's octant.
+template <typename real, typename Put> __device__ inline void cp_residual_restrict(CpTile<real> &S, real *R, Put put) {
+	const int t = threadIdx.x;
+	for (int c = t; c < 512; c += 256) R[c] = residual_cell<real>(S.H, S.ab[c], S.bb[c], cp_hi(c));
+	__syncthreads();
+	if (t < 64) {
+		int o;
+		const real v = restrict_cell<real>(R, t, o);
+		put(o, v);
+	}
+}
+
+/// Down, one tile, a workgroup of 256: x = `inner` red->black sweeps on A x = b from x = 0.
+template <typename real, typename MEM> __device__ inline void cp_presmooth_tile(CpTile<real> &S, const MgLv<real> &L, int slot, int inner) {
+	const size_t base = (size_t)L.tiles[slot] * 512;
+	cp_load_system<real, MEM>(S, L, base);
+	cp_presmooth<real>(S, inner);
+	for (int c = threadIdx.x; c < 512; c += 256) MEM::st(L.x + base + c, S.H[cp_hi(c)]);
 	__syncthreads();
 }
 
@@ -1205,12 +1178,12 @@ __device__ inline void cp_ring(int r, int &f, int &hidx, int &ncell, int &dx, in
 	f = r >> 6;
 	const int lane = r & 63, a = lane & 7, b = lane >> 3;
 	switch (f) {
-	case 0: hidx = 0 + 10 * (a + 1) + 100 * (b + 1); ncell = b * 64 + a * 8 + 7; dx = -1; dy = a; dz = b; break;
-	case 1: hidx = 9 + 10 * (a + 1) + 100 * (b + 1); ncell = b * 64 + a * 8; dx = 8; dy = a; dz = b; break;
-	case 2: hidx = (a + 1) + 100 * (b + 1); ncell = b * 64 + 56 + a; dx = a; dy = -1; dz = b; break;
-	case 3: hidx = (a + 1) + 90 + 100 * (b + 1); ncell = b * 64 + a; dx = a; dy = 8; dz = b; break;
-	case 4: hidx = (a + 1) + 10 * (b + 1); ncell = 448 + lane; dx = a; dy = b; dz = -1; break;
-	default: hidx = (a + 1) + 10 * (b + 1) + 900; ncell = lane; dx = a; dy = b; dz = 8; break;
+	case 0: hidx = halo_at(-1, a, b); ncell = b * 64 + a * 8 + 7; dx = -1; dy = a; dz = b; break;
+	case 1: hidx = halo_at(8, a, b); ncell = b * 64 + a * 8; dx = 8; dy = a; dz = b; break;
+	case 2: hidx = halo_at(a, -1, b); ncell = b * 64 + 56 + a; dx = a; dy = -1; dz = b; break;
+	case 3: hidx = halo_at(a, 8, b); ncell = b * 64 + a; dx = a; dy = 8; dz = b; break;
+	case 4: hidx = halo_at(a, b, -1); ncell = 448 + lane; dx = a; dy = b; dz = -1; break;
+	default: hidx = halo_at(a, b, 8); ncell = lane; dx = a; dy = b; dz = 8; break;
 	}
 }
 
@@ -1221,11 +1194,8 @@ __device__ inline void cp_residual_restrict_tile(CpTile<real> &S, real *R, const
 	const int *nt = L.nbr + (size_t)slot * MG_NBR_STRIDE;
 	const int tile = nt[6];
 	const size_t base = (size_t)tile * 512;
-	for (int c = t; c < 512; c += 256) {
-		S.ab[c] = L.abits[base + c];
-		S.bb[c] = MEM::ld(L.b + base + c);
-		S.H[cp_hi(c)] = MEM::ld(L.x + base + c);
-	}
+	cp_load_system<real, MEM>(S, L, base);
+	for (int c = t; c < 512; c += 256) S.H[cp_hi(c)] = MEM::ld(L.x + base + c);
 	for (int r = t; r < 384; r += 256) {
 		int f, hidx, ncell, dx, dy, dz;
 		cp_ring(r, f, hidx, ncell, dx, dy, dz);
@@ -1233,37 +1203,9 @@ __device__ inline void cp_residual_restrict_tile(CpTile<real> &S, real *R, const
 		S.H[hidx] = nb >= 0 ? MEM::ld(L.x + (size_t)nb * 512 + ncell) : (real)0;
 	}
 	__syncthreads();
-	for (int c = t; c < 512; c += 256) {
-		const int i = cp_hi(c);
-		const uint32_t a = S.ab[c];
-		real r = (real)0;
-		if (a & AB_UNKNOWN) {
-			const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-			real val = (real)(a & 7) * S.H[i];
-			val = madd01(-F, S.H[i - 1], val);
-			val = madd01(-F, S.H[i - 10], val);
-			val = madd01(-F, S.H[i - 100], val);
-			val = madd01(-(real)((a >> 3) & 1), S.H[i + 1], val);
-			val = madd01(-(real)((a >> 4) & 1), S.H[i + 10], val);
-			val = madd01(-(real)((a >> 5) & 1), S.H[i + 100], val);
-			r = S.bb[c] - val;
-		}
-		R[c] = r;
-	}
-	__syncthreads();
-	if (t < 64) {  // one coarse cell each: its 8 children in the order of the pair sums and the two shuffle steps
-		const int X = t & 3, Y = (t >> 2) & 3, Z = t >> 4;
-		auto pair = [&](int x, int y) { real p = R[x + 8 * y + 64 * (2 * Z)]; p += R[x + 8 * y + 64 * (2 * Z + 1)]; return p; };
-		real v = pair(2 * X, 2 * Y);
-		v += pair(2 * X + 1, 2 * Y);
-		real w = pair(2 * X, 2 * Y + 1);
-		w += pair(2 * X + 1, 2 * Y + 1);
-		v += w;
-		int tx, ty, tz;
-		tile_coords(L.g, tile, tx, ty, tz);
-		const int ptile = (tx >> 1) + gc.ntx * ((ty >> 1) + gc.nty * (tz >> 1));
-		MEM::st(b_coarse + (size_t)ptile * 512 + ((tz & 1) * 4 + Z) * 64 + ((ty & 1) * 4 + Y) * 8 + (tx & 1) * 4 + X, (real)0.5 * v);
-	}
+	const MgOctant oc = mg_octant(L.g, gc, tile);
+	real *out = b_coarse + (size_t)oc.ptile * 512 + oc.off;
+	cp_residual_restrict<real>(S, R, [&](int o, real v) { MEM::st(out + o, v); });
 	__syncthreads();
 }
 
@@ -1298,30 +1240,18 @@ __device__ inline void cp_prolong_postsmooth_tile(CpTile<real> &S, const MgLv<re
 		S.H[hidx] = v;
 	}
 	__syncthreads();
-	for (int it = 0; it < inner; ++it) {
-		cp_half_sweep<real>(S, 1);
-		cp_half_sweep<real>(S, 0);
-	}
+	cp_sweeps<real>(S, inner, 1);
 	for (int c = t; c < 512; c += 256) MEM::st(L.y + base + c, S.H[cp_hi(c)]);
 	__syncthreads();
 }
 
 /// Coarsest level (a single tile): nsw red->black sweeps followed by nsw black->red sweeps from zero (coarsest_tile, cell-parallel).
 template <typename real, typename MEM> __device__ inline void cp_coarsest_tile(CpTile<real> &S, const MgLv<real> &L, int nsw) {
-	const int t = threadIdx.x;
 	const size_t base = (size_t)L.tiles[0] * 512;
-	for (int c = t; c < 512; c += 256) {
-		S.ab[c] = L.abits[base + c];
-		S.bb[c] = MEM::ld(L.b + base + c);
-	}
-	for (int i = t; i < LFA_HALO_CELLS; i += 256) S.H[i] = (real)0;
-	__syncthreads();
-	for (int q = 0; q < 2 * nsw; ++q) {
-		const int fc = q < nsw ? 0 : 1;
-		cp_half_sweep<real>(S, fc);
-		cp_half_sweep<real>(S, fc ^ 1);
-	}
-	for (int c = t; c < 512; c += 256) MEM::st(L.y + base + c, S.H[cp_hi(c)]);
+	cp_load_system<real, MEM>(S, L, base);
+	cp_presmooth<real>(S, nsw);
+	cp_sweeps<real>(S, nsw, 1);
+	for (int c = threadIdx.x; c < 512; c += 256) MEM::st(L.y + base + c, S.H[cp_hi(c)]);
 	__syncthreads();
 }
 
@@ -1422,9 +1352,9 @@ __device__ inline unsigned co_xcc_id() {
 /// raises the abort word and RETURNS like any other: the workgroup runs on with void data, every later wait of the launch leaves
 /// at its first slow poll, the kernel ends within a millisecond and the host, which finds the word at its next poll, discards the
 /// solve. (A uniform early exit would need a workgroup-wide OR per wait: two barriers and an LDS round trip in a kernel whose
-/// phases are 2 us - measured: 47 -> 53 us per launch at C4.) Always returns true.
+/// phases are 2 us - measured: 47 -> 53 us per launch at C4.)
 template <typename MEM>
-__device__ inline bool co_wait(const unsigned *flag, const int *dep, int n, unsigned tag, int *abort_word) {
+__device__ inline void co_wait(const unsigned *flag, const int *dep, int n, unsigned tag, int *abort_word) {
 	if ((int)threadIdx.x < n) {
 		const int d = dep[threadIdx.x];
 		if (d >= 0) {
@@ -1447,7 +1377,6 @@ __device__ inline bool co_wait(const unsigned *flag, const int *dep, int n, unsi
 		}
 	}
 	__syncthreads();
-	return true;
 }
 /// All threads: this workgroup's stores so far have been acknowledged; then the tile's flag is raised.
 template <typename MEM> __device__ inline void co_post(unsigned *flag, int tile, unsigned tag) {
@@ -1463,7 +1392,7 @@ struct CoThread {
 		t = threadIdx.x; wg = wg_;
 		qx = t & 7; qy = (t >> 3) & 7; qj = t >> 6;
 		c0 = qx + 8 * qy + 128 * qj; c1 = c0 + 64;
-		h0 = (qx + 1) + 10 * (qy + 1) + 100 * (2 * qj + 1); h1 = h0 + 100;
+		h0 = halo_at(qx, qy, 2 * qj); h1 = h0 + 100;
 	}
 };
 /// One half sweep of colour `colour` on the halo block H with the coefficients of the thread's two cells.
@@ -1472,40 +1401,6 @@ __device__ inline void co_half_sweep(const CoThread &T, real *H, uint32_t a0, ui
 	const int k = (T.qx + T.qy + colour) & 1;
 	gs_cell<real>(H, k ? a1 : a0, k ? b1 : b0, k ? T.h1 : T.h0);
 	__syncthreads();
-}
-/// Residual b - A x of the thread's two cells from the halo block (unscaled operator), term by term as cp_residual_restrict_tile.
-template <typename real> __device__ inline real co_residual_cell(const real *H, uint32_t a, real b, int i) {
-	real r = (real)0;
-	if (a & AB_UNKNOWN) {
-		const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-		real val = (real)(a & 7) * H[i];
-		val = madd01(-F, H[i - 1], val);
-		val = madd01(-F, H[i - 10], val);
-		val = madd01(-F, H[i - 100], val);
-		val = madd01(-(real)((a >> 3) & 1), H[i + 1], val);
-		val = madd01(-(real)((a >> 4) & 1), H[i + 10], val);
-		val = madd01(-(real)((a >> 5) & 1), H[i + 100], val);
-		r = b - val;
-	}
-	return r;
-}
-/// Restriction of the residuals in R (512 cells of tile `tile` of level grid g) to its share of the parent level's right-hand
-/// side: half the sum over the 8 children, in the order of the pair sums and the two shuffle steps of residual_restrict_tile.
-template <typename real, typename MEM>
-__device__ inline void co_restrict_store(const CoThread &T, const real *R, const GridDims &g, const GridDims &gc, int tile, real *b_coarse) {
-	if (T.t < 64) {
-		const int X = T.t & 3, Y = (T.t >> 2) & 3, Z = T.t >> 4;
-		auto pair = [&](int x, int y) { real p = R[x + 8 * y + 64 * (2 * Z)]; p += R[x + 8 * y + 64 * (2 * Z + 1)]; return p; };
-		real v = pair(2 * X, 2 * Y);
-		v += pair(2 * X + 1, 2 * Y);
-		real w = pair(2 * X, 2 * Y + 1);
-		w += pair(2 * X + 1, 2 * Y + 1);
-		v += w;
-		int tx, ty, tz;
-		tile_coords(g, tile, tx, ty, tz);
-		const int ptile = (tx >> 1) + gc.ntx * ((ty >> 1) + gc.nty * (tz >> 1));
-		MEM::st(b_coarse + (size_t)ptile * 512 + ((tz & 1) * 4 + Z) * 64 + ((ty & 1) * 4 + Y) * 8 + (tx & 1) * 4 + X, (real)0.5 * v);
-	}
 }
 /// dep[0..8) = the active child tiles (level below, grid gf) of `tile` (grid g), -1 where there is none.
 __device__ inline void co_child_deps(const CoThread &T, int *dep, const GridDims &g, const GridDims &gf, int tile, int child_mask) {
@@ -1573,7 +1468,6 @@ __device__ inline unsigned long long co_tagged(unsigned tag, float v) { return (
 __device__ inline void co_put(unsigned long long *p, unsigned tag, float v) {
 	__hip_atomic_store(p, co_tagged(tag, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ inline void co_put(unsigned long long *, unsigned, double) {}  // (never called: TAGGED is fp32 only)
 /// Polls N words (p[k] == nullptr: none, the value stays 0) until each carries `tag`; all N loads of a round are in flight
 /// together. A wait that passes the ceiling raises the abort word and returns what it has (see co_wait).
 template <int N> __device__ inline void co_get(const unsigned long long *const (&p)[N], unsigned tag, int *abort_word, float (&v)[N]) {
@@ -1604,24 +1498,6 @@ template <int N> __device__ inline void co_get(const unsigned long long *const (
 	}
 #pragma unroll
 	for (int k = 0; k < N; ++k) v[k] = __uint_as_float((unsigned)w[k]);
-}
-/// co_restrict_store with the parent's share going out as tagged words.
-template <typename real>
-__device__ inline void co_restrict_put(const CoThread &T, const real *R, const GridDims &g, const GridDims &gc, int tile, unsigned long long *bq,
-                                       unsigned tag) {
-	if (T.t < 64) {
-		const int X = T.t & 3, Y = (T.t >> 2) & 3, Z = T.t >> 4;
-		auto pair = [&](int x, int y) { real p = R[x + 8 * y + 64 * (2 * Z)]; p += R[x + 8 * y + 64 * (2 * Z + 1)]; return p; };
-		real v = pair(2 * X, 2 * Y);
-		v += pair(2 * X + 1, 2 * Y);
-		real w = pair(2 * X, 2 * Y + 1);
-		w += pair(2 * X + 1, 2 * Y + 1);
-		v += w;
-		int tx, ty, tz;
-		tile_coords(g, tile, tx, ty, tz);
-		const int ptile = (tx >> 1) + gc.ntx * ((ty >> 1) + gc.nty * (tz >> 1));
-		co_put(bq + (size_t)ptile * 512 + ((tz & 1) * 4 + Z) * 64 + ((ty & 1) * 4 + Y) * 8 + (tx & 1) * 4 + X, tag, (real)0.5 * v);
-	}
 }
 /// The thread's two right-hand-side values of a tile whose children hand their shares over as tagged words: a cell of an
 /// inactive child (bit of `child_mask` clear) is zero and nobody writes it.
@@ -1745,7 +1621,7 @@ __device__ inline bool co_static(const MgCo<real> &P, const CoThread &T, CoLevel
 /// TAGGED: what the workgroups hand to each other travels as {tag, value} words (P.xq) instead of through the level arrays + ready
 /// flags - see co_put / co_get; the first level's right-hand side (in) and result (out) stay plain: other kernels own them.
 template <typename real, typename MEM, bool TAGGED>
-__device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<real> *st, real *R, int *dep, unsigned tag, int lmax,
+__device__ inline void co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<real> *st, real *R, int *dep, unsigned tag, int lmax,
                                 bool b_prefetched, bool post_first_y) {
 	const int t = T.t, c0 = T.c0, c1 = T.c1, h0 = T.h0, h1 = T.h1;
 	auto xq = [&](int l) { return P.xq[l]; };
@@ -1767,7 +1643,7 @@ __device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<
 		} else if (waited) {
 			const GridDims &gf = P.lv[l - 1].g;
 			co_child_deps(T, dep, L.g, gf, tile, S.nb[7]);
-			if (!co_wait<MEM>(P.ready[l - 1] + gf.nt, dep, 8, tag, P.abort)) return false;
+			co_wait<MEM>(P.ready[l - 1] + gf.nt, dep, 8, tag, P.abort);
 			b0 = MEM::ld(L.b + base + c0);
 			b1 = MEM::ld(L.b + base + c1);
 			S.b[c0] = b0;
@@ -1795,19 +1671,22 @@ __device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<
 			if (!faulty) co_post<MEM>(P.ready[l], tile, tag);
 			if (t < 6) dep[t] = S.nb[t];
 			__syncthreads();
-			if (!co_wait<MEM>(P.ready[l], dep, 6, tag, P.abort)) return false;
+			co_wait<MEM>(P.ready[l], dep, 6, tag, P.abort);
 			co_load_ring<real, MEM>(T, S.H, S.nb, L.x);
 		}
-		R[c0] = co_residual_cell<real>(S.H, a0, b0, h0);
-		R[c1] = co_residual_cell<real>(S.H, a1, b1, h1);
+		R[c0] = residual_cell<real>(S.H, a0, b0, h0);
+		R[c1] = residual_cell<real>(S.H, a1, b1, h1);
 		__syncthreads();
-		if (TAGGED) {
-			co_restrict_put<real>(T, R, L.g, P.lv[l + 1].g, tile, bq(l + 1), tag);
-			__syncthreads();  // (R is rewritten by the next level)
-		} else {
-			co_restrict_store<real, MEM>(T, R, L.g, P.lv[l + 1].g, tile, P.lv[l + 1].b);
-			co_post<MEM>(P.ready[l] + nt, tile, tag);
+		if (t < 64) {  // the tile's share of the parent's right-hand side
+			int o;
+			const real v = restrict_cell<real>(R, t, o);
+			const MgOctant oc = mg_octant(L.g, P.lv[l + 1].g, tile);
+			const size_t j = (size_t)oc.ptile * 512 + oc.off + o;
+			if (TAGGED) co_put(bq(l + 1) + j, tag, v);
+			else MEM::st(P.lv[l + 1].b + j, v);
 		}
+		if (TAGGED) __syncthreads();  // (R is rewritten by the next level)
+		else co_post<MEM>(P.ready[l] + nt, tile, tag);
 	}
 	// ---- coarsest level (one tile, workgroup 0): nsw sweeps red->black, nsw black->red from zero
 	if (T.wg == 0) {
@@ -1824,7 +1703,7 @@ __device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<
 		} else if (waited) {
 			const GridDims &gf = P.lv[l - 1].g;
 			co_child_deps(T, dep, L.g, gf, tile, S.nb[7]);
-			if (!co_wait<MEM>(P.ready[l - 1] + gf.nt, dep, 8, tag, P.abort)) return false;
+			co_wait<MEM>(P.ready[l - 1] + gf.nt, dep, 8, tag, P.abort);
 			b0 = MEM::ld(L.b + base + c0);
 			b1 = MEM::ld(L.b + base + c1);
 		} else {
@@ -1859,7 +1738,7 @@ __device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<
 			co_get_correction<real>(T, S.H, a0, a1, S.rab, S.nb, L.g, gc, tile, yq(l + 1), tag, P.abort);
 		} else {
 			co_parent_deps(T, dep, L.g, gc, S.nb);
-			if (!co_wait<MEM>(P.ready[l + 1] + 2 * gc.nt, dep, 7, tag, P.abort)) return false;
+			co_wait<MEM>(P.ready[l + 1] + 2 * gc.nt, dep, 7, tag, P.abort);
 			co_add_correction<real, MEM>(T, S.H, a0, a1, S.rab, S.nb, L.g, gc, tile, P.lv[l + 1].y);
 		}
 		for (int it = 0; it < P.inner; ++it) {
@@ -1875,7 +1754,6 @@ __device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<
 			if (l > P.first || post_first_y) co_post<MEM>(P.ready[l] + 2 * L.g.nt, tile, tag);
 		}
 	}
-	return true;
 }
 
 // ---- the level above, fused into the launch in LAUNCH ORDER (round 5, tagged hand-off only)
@@ -1893,19 +1771,10 @@ __device__ inline bool co_cycle(const MgCo<real> &P, const CoThread &T, CoLevel<
 /// Phase 1 of the top level: cp_presmooth_tile with the iterate going out as tagged words.
 template <typename real>
 __device__ inline void top_presmooth(CpTile<real> &S, const MgLv<real> &L, int slot, int inner, unsigned long long *xq, unsigned tag) {
-	const int t = threadIdx.x;
 	const size_t base = (size_t)L.tiles[slot] * 512;
-	for (int c = t; c < 512; c += 256) {
-		S.ab[c] = L.abits[base + c];
-		S.bb[c] = L.b[base + c];  // (restricted by the previous launch)
-	}
-	for (int i = t; i < LFA_HALO_CELLS; i += 256) S.H[i] = (real)0;
-	__syncthreads();
-	for (int it = 0; it < inner; ++it) {
-		cp_half_sweep<real>(S, 0);
-		cp_half_sweep<real>(S, 1);
-	}
-	for (int c = t; c < 512; c += 256) co_put(xq + base + c, tag, S.H[cp_hi(c)]);
+	cp_load_system<real, MemPlain>(S, L, base);  // (the right-hand side: restricted by the previous launch)
+	cp_presmooth<real>(S, inner);
+	for (int c = threadIdx.x; c < 512; c += 256) co_put(xq + base + c, tag, S.H[cp_hi(c)]);
 }
 /// Phase 2: cp_residual_restrict_tile; the iterate (own cells and ring) comes in, the parent's share goes out, as tagged words.
 template <typename real>
@@ -1922,10 +1791,7 @@ __device__ inline void top_residual_restrict(CpTile<real> &S, real *R, const MgL
 	const int nb0 = nt[f0], nb1 = r1 < 384 ? nt[f1] : -1;
 	const unsigned long long *const p[4] = {xq + base + t, xq + base + t + 256, nb0 >= 0 ? xq + (size_t)nb0 * 512 + n0 : nullptr,
 	                                        nb1 >= 0 ? xq + (size_t)nb1 * 512 + n1 : nullptr};
-	for (int c = t; c < 512; c += 256) {
-		S.ab[c] = L.abits[base + c];
-		S.bb[c] = L.b[base + c];
-	}
+	cp_load_system<real, MemPlain>(S, L, base);
 	float v[4];
 	co_get<4>(p, tag, abort_word, v);
 	S.H[cp_hi(t)] = (real)v[0];
@@ -1933,37 +1799,9 @@ __device__ inline void top_residual_restrict(CpTile<real> &S, real *R, const MgL
 	S.H[h0] = (real)v[2];  // (0 where the neighbour tile is inactive)
 	if (r1 < 384) S.H[h1] = (real)v[3];
 	__syncthreads();
-	for (int c = t; c < 512; c += 256) {
-		const int i = cp_hi(c);
-		const uint32_t a = S.ab[c];
-		real r = (real)0;
-		if (a & AB_UNKNOWN) {
-			const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-			real val = (real)(a & 7) * S.H[i];
-			val = madd01(-F, S.H[i - 1], val);
-			val = madd01(-F, S.H[i - 10], val);
-			val = madd01(-F, S.H[i - 100], val);
-			val = madd01(-(real)((a >> 3) & 1), S.H[i + 1], val);
-			val = madd01(-(real)((a >> 4) & 1), S.H[i + 10], val);
-			val = madd01(-(real)((a >> 5) & 1), S.H[i + 100], val);
-			r = S.bb[c] - val;
-		}
-		R[c] = r;
-	}
-	__syncthreads();
-	if (t < 64) {  // one coarse cell each: its 8 children in the order of the pair sums and the two shuffle steps
-		const int X = t & 3, Y = (t >> 2) & 3, Z = t >> 4;
-		auto pair = [&](int x, int y) { real q = R[x + 8 * y + 64 * (2 * Z)]; q += R[x + 8 * y + 64 * (2 * Z + 1)]; return q; };
-		real v2 = pair(2 * X, 2 * Y);
-		v2 += pair(2 * X + 1, 2 * Y);
-		real w = pair(2 * X, 2 * Y + 1);
-		w += pair(2 * X + 1, 2 * Y + 1);
-		v2 += w;
-		int tx, ty, tz;
-		tile_coords(L.g, tile, tx, ty, tz);
-		const int ptile = (tx >> 1) + gc.ntx * ((ty >> 1) + gc.nty * (tz >> 1));
-		co_put(bq_coarse + (size_t)ptile * 512 + ((tz & 1) * 4 + Z) * 64 + ((ty & 1) * 4 + Y) * 8 + (tx & 1) * 4 + X, tag, (real)0.5 * v2);
-	}
+	const MgOctant oc = mg_octant(L.g, gc, tile);
+	unsigned long long *out = bq_coarse + (size_t)oc.ptile * 512 + oc.off;
+	cp_residual_restrict<real>(S, R, [&](int o, real r) { co_put(out + o, tag, r); });
 }
 /// Phase 3: cp_prolong_postsmooth_tile; the iterate and the parents' corrections come in as tagged words, the result goes to the
 /// level's plain array (the finer level's launch reads it).
@@ -2016,10 +1854,7 @@ __device__ inline void top_prolong_postsmooth(CpTile<real> &S, const MgLv<real> 
 		if (r1 < 384) S.H[h1] = g1;
 	}
 	__syncthreads();
-	for (int it = 0; it < inner; ++it) {
-		cp_half_sweep<real>(S, 1);
-		cp_half_sweep<real>(S, 0);
-	}
+	cp_sweeps<real>(S, inner, 1);
 	for (int c = t; c < 512; c += 256) L.y[base + c] = S.H[cp_hi(c)];
 }
 
@@ -2079,7 +1914,7 @@ __global__ void __launch_bounds__(256) k_mg_coarse(MgCo<real> P, const int *stat
 		if (T.wg < P.lv[l].n_tiles) lmax = l;
 	const bool with_top = n_top > 0;
 	if (!co_static<real, MEM>(P, T, st, lmax, state, !with_top)) return;
-	(void)co_cycle<real, MEM, TAGGED>(P, T, st, R, dep, P.tag, lmax, !with_top, with_top);
+	co_cycle<real, MEM, TAGGED>(P, T, st, R, dep, P.tag, lmax, !with_top, with_top);
 }
 
 /// The small levels in ONE workgroup of 16 waves: down from level `first` to the single-tile level, the coarsest solve,
@@ -2097,7 +1932,7 @@ template <typename real> struct MgTail {
 /// A single tile has no active neighbours, so the ring of the halo block stays zero. One wave doing all of this alone
 /// (4 cells per lane and colour, 24 dependent half sweeps per V-cycle) spent 22 of the tail's 35 us on instruction latency
 /// (s_memtime stamps). Same operations in the same order as presmooth_tile / residual_restrict_tile / coarsest_tile /
-/// prolong_postsmooth_tile: bit-identical results (tested against LFA_MG_NO_CHAIN=1).
+/// prolong_postsmooth_tile: bit-identical results (tested against k_mg_coarse, which takes these levels in every other mode).
 template <typename real>
 __device__ inline void single_tile_chain(const MgTail<real> &T, real *H, real (*cb)[512], real (*cx)[512], real (*cy)[512], real *R,
                                          uint8_t *cab_) {
@@ -2106,14 +1941,9 @@ __device__ inline void single_tile_chain(const MgTail<real> &T, real *H, real (*
 	const bool cellwise = t < 512, colourwise = t < 256;
 	// cell of a thread in the cell-wise phases, and its halo index
 	const int cell = t & 511, px = cell & 7, py = (cell >> 3) & 7, pz = cell >> 6;
-	const int hi = (px + 1) + 10 * (py + 1) + 100 * (pz + 1);
-	// cell of a thread in a half sweep of colour c: column (qx, qy), z = 2 j + ((qx + qy + c) & 1)
-	const int qx = t & 7, qy = (t >> 3) & 7, qj = (t >> 6) & 3;
+	const int hi = halo_at(px, py, pz);
 	auto half_sweep = [&](int k, int colour) {
-		if (colourwise) {
-			const int z = 2 * qj + ((qx + qy + colour) & 1), c = qx + 8 * qy + 64 * z;
-			gs_cell<real>(H, cab[k][c], cb[k][c], (qx + 1) + 10 * (qy + 1) + 100 * (z + 1));
-		}
+		if (colourwise) gs_half_sweep<real>(H, cab[k], cb[k], t, colour);
 		__syncthreads();
 	};
 	for (int i = t; i < LFA_HALO_CELLS; i += MG_TAIL_WAVES * 64) H[i] = (real)0;
@@ -2135,33 +1965,13 @@ __device__ inline void single_tile_chain(const MgTail<real> &T, real *H, real (*
 		}
 		if (cellwise) {
 			cx[k][cell] = H[hi];
-			const uint32_t a = cab[k][cell];
-			real r = (real)0;
-			if (a & AB_UNKNOWN) {
-				const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-				real val = (real)(a & 7) * H[hi];
-				val = madd01(-F, H[hi - 1], val);
-				val = madd01(-F, H[hi - 10], val);
-				val = madd01(-F, H[hi - 100], val);
-				val = madd01(-(real)((a >> 3) & 1), H[hi + 1], val);
-				val = madd01(-(real)((a >> 4) & 1), H[hi + 10], val);
-				val = madd01(-(real)((a >> 5) & 1), H[hi + 100], val);
-				r = cb[k][cell] - val;
-			}
-			R[cell] = r;
+			R[cell] = residual_cell<real>(H, cab[k][cell], cb[k][cell], hi);
 		}
 		__syncthreads();
-		if (t < 64) {  // one coarse cell each: its 8 children in the order of the pair sums and the two shuffle steps
-			const int X = t & 3, Y = (t >> 2) & 3, Z = t >> 4;
-			auto pair = [&](int x, int y) { real p = R[x + 8 * y + 64 * (2 * Z)]; p += R[x + 8 * y + 64 * (2 * Z + 1)]; return p; };
-			real v = pair(2 * X, 2 * Y);
-			v += pair(2 * X + 1, 2 * Y);
-			real w = pair(2 * X, 2 * Y + 1);
-			w += pair(2 * X + 1, 2 * Y + 1);
-			v += w;
-			int tx, ty, tz;
-			tile_coords(L.g, L.tiles[0], tx, ty, tz);
-			cb[k + 1][((tz & 1) * 4 + Z) * 64 + ((ty & 1) * 4 + Y) * 8 + (tx & 1) * 4 + X] = (real)0.5 * v;
+		if (t < 64) {  // the tile's octant of the next level's right-hand side (the rest stays zero)
+			int o;
+			const real v = restrict_cell<real>(R, t, o);
+			cb[k + 1][mg_octant(L.g, T.lv[s1 + k + 1].g, L.tiles[0]).off + o] = v;
 		}
 		__syncthreads();
 	}
@@ -2226,7 +2036,7 @@ __global__ void __launch_bounds__(MG_TAIL_WAVES * 64) k_mg_tail(MgTail<real> T, 
 			prolong_postsmooth_tile<real>(L, T.lv[l + 1].g, T.lv[l + 1].y, slot, h, lane, bb, T.inner);
 			const size_t base = (size_t)L.tiles[slot] * 512;
 #pragma unroll
-			for (int zz = 0; zz < 8; ++zz) L.y[base + zz * 64 + lane] = h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)];
+			for (int zz = 0; zz < 8; ++zz) L.y[base + zz * 64 + lane] = h[halo_at(lx, ly, zz)];
 		}
 		__syncthreads();
 	}
@@ -3189,9 +2999,10 @@ k_mg_solve_closed(const int *ptiles, int n_ptiles, const uint8_t *closed, const 
 			real rmax = (real)0;
 #pragma unroll
 			for (int zz = 0; zz < 8; ++zz) {
-				const int i = (lx + 1) + 10 * (ly + 1) + 100 * (zz + 1);
+				const int i = halo_at(lx, ly, zz);
 				const uint32_t a = ab[zz];
 				if (a & AB_UNKNOWN) {
+					// (NOT stencil_row: this test rounds differently, and another rounding changes when the sweeps stop)
 					const real F = (a & AB_FLUID) ? (real)1 : (real)0;
 					real val = (real)(a & 7) * h[i];
 					val -= F * (h[i - 1] + h[i - 10] + h[i - 100]);
@@ -3210,7 +3021,7 @@ k_mg_solve_closed(const int *ptiles, int n_ptiles, const uint8_t *closed, const 
 		}
 		if (bad && lane == 0) state[1] = 1;
 #pragma unroll
-		for (int zz = 0; zz < 8; ++zz) p[base + zz * 64 + lane] = h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] * inv_scale;
+		for (int zz = 0; zz < 8; ++zz) p[base + zz * 64 + lane] = h[halo_at(lx, ly, zz)] * inv_scale;
 		MG_FENCE();
 	}
 }

@@ -1,4 +1,4 @@
-// libfluid_amd/csrc/pcg.h -- shared constants of the pressure-solve kernels.
+// libfluid_amd/csrc/pcg.h -- shared constants and cell / tile primitives of the pressure-solve kernels.
 #pragma once
 #include "common.h"
 
@@ -24,6 +24,73 @@ static inline int pcg_grid_uncapped(int n_ptiles) {
 	int g = (n_ptiles + PCG_WAVES - 1) / PCG_WAVES;
 	if (g < 1) g = 1;
 	return g < PCG_MAX_GRID ? g : PCG_MAX_GRID;
+}
+
+// ---- cell and tile primitives of the solve's kernels (pcg.hip, mg.hip). The execution forms of the V-cycle - a wave per tile, the
+// finest level's pipelines, a workgroup per tile, the dataflow and launch-order forms of k_mg_coarse, the single-tile chain - must
+// agree bit for bit (tested): each of them calls these, none types the arithmetic out again.
+/// Index of cell (x, y, z) of a tile, each -1 .. 8, in the tile's 10^3 halo block.
+/// (A macro on purpose: as a function, even one inlined at once, the compiler associates the address sums differently in twenty
+/// kernels, and k_mg_solve_closed<float> goes from 168 to 178 VGPRs, from 3 to 2 waves per SIMD - tools/kernel_diff.py.)
+#define halo_at(x, y, z) (((x) + 1) + 10 * ((y) + 1) + 100 * ((z) + 1))
+/// The six faces of a halo block, a wave's worth: lane = (lx, ly) over the two in-face axes; v[6] = x-, x+, y-, y+, z-, z+.
+/// (A macro for the same reason: as a function it costs k_pcg_a<float, true, false> 8 VGPRs, a wave per SIMD, and the fp64
+/// k_mg_prolong_postsmooth five more spills.)
+#define store_halo_faces(h, lx, ly, v) \
+	do {                               \
+		(h)[halo_at(-1, lx, ly)] = (v)[0]; \
+		(h)[halo_at(8, lx, ly)] = (v)[1];  \
+		(h)[halo_at(lx, -1, ly)] = (v)[2]; \
+		(h)[halo_at(lx, 8, ly)] = (v)[3];  \
+		(h)[halo_at(lx, ly, -1)] = (v)[4]; \
+		(h)[halo_at(lx, ly, 8)] = (v)[5];  \
+	} while (0)
+/// Halo block of a tile-major vector: interior + the six faces of the neighbour tiles nb[0..6) (0 where there is none).
+/// `ld(j)` reads element j of the vector.
+template <typename real, typename Load>
+__device__ inline void load_halo(real *h, Load ld, size_t base, const int (&nb)[6], int lane, int lx, int ly) {
+#pragma unroll
+	for (int zz = 0; zz < 8; ++zz) h[halo_at(lx, ly, zz)] = ld(base + zz * 64 + lane);
+	const size_t cell[6] = {(size_t)ly * 64 + lx * 8 + 7, (size_t)ly * 64 + lx * 8, (size_t)ly * 64 + 56 + lx, (size_t)ly * 64 + lx,
+	                        (size_t)7 * 64 + lane, (size_t)lane};
+	real v[6];
+#pragma unroll
+	for (int k = 0; k < 6; ++k) v[k] = nb[k] >= 0 ? ld((size_t)nb[k] * 512 + cell[k]) : (real)0;
+	store_halo_faces(h, lx, ly, v);
+}
+/// Row i (halo index) of the UNSCALED 7-point operator, term by term in the order of pressure_solver::_apply_a
+/// (src/pressure_solver.cpp:334-362): a = the cell's A byte (non-solid neighbour count, "positive neighbour is fluid" bits).
+template <typename real> __device__ inline real stencil_row(const real *H, uint32_t a, int i) {
+	const real F = (a & AB_FLUID) ? (real)1 : (real)0;
+	real val = (real)(a & 7) * H[i];
+	val = madd01(-F, H[i - 1], val);
+	val = madd01(-F, H[i - 10], val);
+	val = madd01(-F, H[i - 100], val);
+	val = madd01(-(real)((a >> 3) & 1), H[i + 1], val);
+	val = madd01(-(real)((a >> 4) & 1), H[i + 10], val);
+	val = madd01(-(real)((a >> 5) & 1), H[i + 100], val);
+	return val;
+}
+/// Residual b - A x of an unknown (unscaled operator), 0 for every other cell.
+template <typename real> __device__ inline real residual_cell(const real *H, uint32_t a, real b, int i) {
+	real r = (real)0;
+	if (a & AB_UNKNOWN) r = b - stencil_row<real>(H, a, i);
+	return r;
+}
+/// Maximum that keeps a NaN.
+__device__ inline double nan_max(double x, double y) { return (x != x || y != y) ? NAN : (y > x ? y : x); }
+/// The stopping rule of pressure_solver::solve (src/pressure_solver.cpp:54-58) on rmax, the signed maximum of the residual of
+/// iteration `slot`: a NaN or rmax < tol ends the solve with iteration count slot + 1.
+__device__ inline bool verdict_stops(double rmax, double tol) { return rmax != rmax || rmax < tol; }
+/// ... recorded, by ONE thread: the history entry always; when the solve ends the NaN word, the residual beside the state words (the
+/// host reads it with them: no read-back of its own) and the iteration count, which the kernels queued behind see and return.
+__device__ inline void record_verdict(int *state, double *hist, int slot, double rmax, bool stops) {
+	hist[slot] = rmax;
+	if (stops) {
+		if (rmax != rmax) state[1] = 1;
+		*(double *)(state + 16) = rmax;
+		state[0] = slot + 1;
+	}
 }
 
 int lfa_build_rhs(lfa_sim *s, double dt);

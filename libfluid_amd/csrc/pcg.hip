@@ -83,7 +83,6 @@ __device__ inline void reduce_partials_sum2(const double *pa, int na, const doub
 	rb = (lds[4] + lds[5]) + (lds[6] + lds[7]);
 	__syncthreads();
 }
-__device__ inline double nan_max(double x, double y) { return (x != x || y != y) ? NAN : (y > x ? y : x); }
 __device__ inline double reduce_partials_max(const double *part, int n, double *lds) {
 	bool nan = false;
 	double a = strided_partial_max(part, n, nan);
@@ -120,33 +119,16 @@ k_spmv(TileCtx tc, const uint8_t *abits, const real *s, real *z, real scale, dou
 			face_neighbours(tc, tile, nb);
 			const size_t base = (size_t)tile * LFA_TILE_CELLS;
 			WAVE_SYNC();
-#pragma unroll
-			for (int zz = 0; zz < 8; ++zz) h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = s[base + zz * 64 + lane];
-			// faces: lane = (a, b) over the two in-face axes
-			h[0 + 10 * (lx + 1) + 100 * (ly + 1)] = nb[0] >= 0 ? s[(size_t)nb[0] * 512 + ly * 64 + lx * 8 + 7] : (real)0;
-			h[9 + 10 * (lx + 1) + 100 * (ly + 1)] = nb[1] >= 0 ? s[(size_t)nb[1] * 512 + ly * 64 + lx * 8 + 0] : (real)0;
-			h[(lx + 1) + 10 * 0 + 100 * (ly + 1)] = nb[2] >= 0 ? s[(size_t)nb[2] * 512 + ly * 64 + 7 * 8 + lx] : (real)0;
-			h[(lx + 1) + 10 * 9 + 100 * (ly + 1)] = nb[3] >= 0 ? s[(size_t)nb[3] * 512 + ly * 64 + 0 * 8 + lx] : (real)0;
-			h[(lx + 1) + 10 * (ly + 1) + 100 * 0] = nb[4] >= 0 ? s[(size_t)nb[4] * 512 + 7 * 64 + lane] : (real)0;
-			h[(lx + 1) + 10 * (ly + 1) + 100 * 9] = nb[5] >= 0 ? s[(size_t)nb[5] * 512 + 0 * 64 + lane] : (real)0;
+			load_halo<real>(h, [&](size_t j) { return s[j]; }, base, nb, lane, lx, ly);
 			WAVE_SYNC();
 #pragma unroll
 			for (int zz = 0; zz < 8; ++zz) {
-				const int i = (lx + 1) + 10 * (ly + 1) + 100 * (zz + 1);
+				const int i = halo_at(lx, ly, zz);
 				const uint8_t a = abits[base + zz * 64 + lane];
 				real out = (real)0;
 				if (a & AB_UNKNOWN) {
-					const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-					const real si = h[i];
-					real val = (real)(a & 7) * si;
-					val = madd01(-F, h[i - 1], val);
-					val = madd01(-F, h[i - 10], val);
-					val = madd01(-F, h[i - 100], val);
-					val = madd01(-(real)((a >> 3) & 1), h[i + 1], val);
-					val = madd01(-(real)((a >> 4) & 1), h[i + 10], val);
-					val = madd01(-(real)((a >> 5) & 1), h[i + 100], val);
-					out = scale * val;
-					acc += (double)out * (double)si;
+					out = scale * stencil_row<real>(h, a, i);
+					acc += (double)out * (double)h[i];
 				}
 				z[base + zz * 64 + lane] = out;
 			}
@@ -209,7 +191,7 @@ k_axpy_max(TileCtx tc, const uint8_t *abits, Vecs<real> v, const double *part_si
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		double r = lds[0];
-		for (int i = 1; i < 4; ++i) r = (r != r || lds[i] != lds[i]) ? NAN : (lds[i] > r ? lds[i] : r);
+		for (int i = 1; i < 4; ++i) r = nan_max(r, lds[i]);
 		part_rmax[blockIdx.x] = r;
 	}
 }
@@ -618,17 +600,7 @@ k_check_converged(const double *part_rmax, int n_part, double tol, int iter, int
 	if (gave_up && threadIdx.x == 0 && *gave_up > 0.0 && state[2] == 0) state[2] = 1;
 	if (state[0] >= 0) return;
 	const double rmax = reduce_partials_max(part_rmax, n_part, lds);
-	if (threadIdx.x == 0) {
-		hist[iter] = rmax;
-		if (rmax != rmax) {
-			state[1] = 1;
-			*(double *)(state + 16) = rmax;
-			state[0] = iter + 1;
-		} else if (rmax < tol) {
-			*(double *)(state + 16) = rmax;  // (the host reads it with the state words: no read-back of its own)
-			state[0] = iter + 1;
-		}
-	}
+	if (threadIdx.x == 0) record_verdict(state, hist, iter, rmax, verdict_stops(rmax, tol));
 }
 
 /// The early-out of pressure_solver::solve (src/pressure_solver.cpp:28-35: sum b^2 < 1e-6 returns p = 0, residual 0, 0 iterations)
@@ -1152,7 +1124,7 @@ k_pcg_b(const int *__restrict__ ptiles, int n_ptiles, const uint8_t *__restrict_
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		double r = red[0];
-		for (int i = 1; i < 4; ++i) r = (r != r || red[i] != red[i]) ? NAN : (red[i] > r ? red[i] : r);
+		for (int i = 1; i < 4; ++i) r = nan_max(r, red[i]);
 		part_rmax[blk] = r;
 		part_sigma_new[blk] = (red[8] + red[9]) + (red[10] + red[11]);
 	}
@@ -1224,15 +1196,8 @@ k_pcg_a(int n_ptiles, const int *__restrict__ nbr, const uint8_t *__restrict__ a
 		// stopping rule of pressure_solver::solve (src/pressure_solver.cpp:54-58) on the residual of iteration iter-1;
 		// every workgroup evaluates it on the same partials, workgroup 0 records it
 		const double rmax = reduce_partials_max(part_rmax, n_rmax, lds);
-		const bool stop = rmax != rmax || rmax < tol;
-		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			hist[iter - 1] = rmax;
-			if (stop) {
-				if (rmax != rmax) state[1] = 1;
-				*(double *)(state + 16) = rmax;
-				state[0] = iter;
-			}
-		}
+		const bool stop = verdict_stops(rmax, tol);
+		if (blockIdx.x == 0 && threadIdx.x == 0) record_verdict(state, hist, iter - 1, rmax, stop);
 		if (stop) return;
 	}
 	real beta = (real)0;
@@ -1254,7 +1219,7 @@ k_pcg_a(int n_ptiles, const int *__restrict__ nbr, const uint8_t *__restrict__ a
 			if (COARSE && (ab[zz] & AB_UNKNOWN)) zj += xc;
 			const real sj = FIRST ? zj : zj + beta * si[zz];
 			if (s_new) s_new[obase + zz * 64 + lane] = sj;  // (nullptr: q = A z alone - the single-reduction CG of slab runs)
-			h[(lx + 1) + 10 * (ly + 1) + 100 * (zz + 1)] = sj;
+			h[halo_at(lx, ly, zz)] = sj;
 		}
 		real fv[6];
 #pragma unroll
@@ -1264,33 +1229,19 @@ k_pcg_a(int n_ptiles, const int *__restrict__ nbr, const uint8_t *__restrict__ a
 			fv[k] = FIRST ? zj : zj + beta * fs[k];
 			fv[k] = fvalid[k] ? fv[k] : (real)0;
 		}
-		h[0 + 10 * (lx + 1) + 100 * (ly + 1)] = fv[0];
-		h[9 + 10 * (lx + 1) + 100 * (ly + 1)] = fv[1];
-		h[(lx + 1) + 10 * 0 + 100 * (ly + 1)] = fv[2];
-		h[(lx + 1) + 10 * 9 + 100 * (ly + 1)] = fv[3];
-		h[(lx + 1) + 10 * (ly + 1) + 100 * 0] = fv[4];
-		h[(lx + 1) + 10 * (ly + 1) + 100 * 9] = fv[5];
+		store_halo_faces(h, lx, ly, fv);
 		slot += stride;
 		if (slot < n_ptiles) load_tile(slot);
 		WAVE_FENCE();
 		double sq = 0.0;
 #pragma unroll
 		for (int zz = 0; zz < 8; ++zz) {
-			const int i = (lx + 1) + 10 * (ly + 1) + 100 * (zz + 1);
+			const int i = halo_at(lx, ly, zz);
 			const uint32_t a = ac[zz];
 			real out = (real)0;
 			if (a & AB_UNKNOWN) {
-				const real F = (a & AB_FLUID) ? (real)1 : (real)0;
-				const real sc = h[i];
-				real val = (real)(a & 7) * sc;
-				val = madd01(-F, h[i - 1], val);
-				val = madd01(-F, h[i - 10], val);
-				val = madd01(-F, h[i - 100], val);
-				val = madd01(-(real)((a >> 3) & 1), h[i + 1], val);
-				val = madd01(-(real)((a >> 4) & 1), h[i + 10], val);
-				val = madd01(-(real)((a >> 5) & 1), h[i + 100], val);
-				out = scale * val;
-				acc += (double)out * (double)sc;
+				out = scale * stencil_row<real>(h, a, i);
+				acc += (double)out * (double)h[i];
 				sq += (double)out;
 			}
 			q[obase + zz * 64 + lane] = out;

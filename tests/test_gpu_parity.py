@@ -494,7 +494,8 @@ def test_pcg_warm_start_converges_to_the_same_pressure_in_fewer_iterations():
 
 @pytest.mark.parametrize("dtype", [lfa.PCG_F32, lfa.PCG_F64])
 @pytest.mark.parametrize("size,block", [((136, 72, 104), ((0, 0, 0), (90, 50, 70))), ((64, 48, 40), ((3, 0, 2), (50, 30, 33))),
-                                        ((200, 120, 96), ((0, 0, 0), (200, 60, 96))), ((368, 16, 368), ((0, 0, 0), (368, 2, 368)))])
+                                        ((200, 120, 96), ((0, 0, 0), (200, 60, 96))), ((368, 16, 368), ((0, 0, 0), (368, 2, 368))),
+                                        ((256, 8, 8), ((0, 0, 0), (8, 8, 8)))])
 def test_multigrid_single_launch_coarse_levels_are_bitwise_the_launch_per_phase_path(dtype, size, block, monkeypatch):
     """k_mg_coarse runs every phase of the coarse levels (pre-smoothing, residual + restriction, coarsest solve, prolongation +
     post-smoothing) inside one launch as dataflow between workgroups: one tile per workgroup and level, resident in LDS, ready
@@ -504,8 +505,12 @@ def test_multigrid_single_launch_coarse_levels_are_bitwise_the_launch_per_phase_
     level 1 (375 tiles) is the launch's first level, and a thin sheet whose level 1 is too large to be inside (more than 512
     tiles) but small enough (at most 1024) to be fused in front of the launch, in launch order: the only grid here with such a
     level. The sheet's active tiles per level are 2116, 529, 144, 36, 9, 4, 1 in every mode; with fp32 vectors the first level in
-    the launch is 1 by default and 2 with LFA_MG_NO_TOP=1 (5 and 8 launches per iteration; 20 with a launch per phase)."""
+    the launch is 1 by default and 2 with LFA_MG_NO_TOP=1 (5 and 8 launches per iteration; 20 with a launch per phase).
+    The rod (256 x 8 x 8, one tile of fluid at its end) has six levels of ONE active tile each: more trailing single-tile levels
+    than the chain of k_mg_tail takes (four), so with a launch per phase level 1 goes through k_mg_tail's wave-per-tile loops -
+    the only grid here that reaches them - and levels 2-5 through its chain; in the other modes levels 1-5 sit inside k_mg_coarse."""
     sheet = size == (368, 16, 368)
+    rod = size == (256, 8, 8)
     res = []
     # "tagged": the default with fp32 vectors - values travel between the workgroups as {tag, value} words (fp64: the same as
     # "flags"); "flags": level arrays + ready flags (LFA_MG_NO_TAGGED=1); "phase": a launch per phase
@@ -528,6 +533,8 @@ def test_multigrid_single_launch_coarse_levels_are_bitwise_the_launch_per_phase_
             its.append(it)
         st = s.solver_stats()
         assert (st["mg_first_level_in_coarse_launch"] >= 1) == (mode != "phase") and st["device_waits_given_up"] == 0, st
+        if rod:
+            assert list(s.mg_level_tiles()[:6]) == [1] * 6
         if sheet:
             assert list(s.mg_level_tiles()[:7]) == [2116, 529, 144, 36, 9, 4, 1]
             if dtype == lfa.PCG_F32 and mode in ("tagged", "tagged-no-top"):
