@@ -219,6 +219,48 @@ int lfa_sample_velocity_collective(lfa_sim *s, const double *xyz, uint64_t n, ui
 /* Device milliseconds of the kernel of the last lfa_sample_velocity (HIP events on the handle's stream; not the copies).
  * LFA_E_INVALID when none has run on the device. */
 int lfa_sample_velocity_time(lfa_sim *s, double *ms);
+/* -- tracers: massless markers on the device ------------------------------------------------------------------------------------
+ * A tracer has an fp64 world position, an fp64 velocity and the cell type at its position. It moves as a PIC particle of the
+ * reference does and is seen by no grid stage (P2G, pressure solve, position correction): dye, debris, foam seeds, streak lines.
+ * What it replaces: per step one lfa_sample_velocity (24 bytes per point up, 24 down), the move on the host, and - to stop a
+ * point at an obstacle - lfa_download_cells (32 bytes per cell) with the host's own copy of _detect_collisions. Step n of the
+ * tracers follows lfa_time_step number n with the same dt:
+ *   1. move     : _advect_particles (src/simulation.cpp:240-248): position += velocity * dt, clamped to [grid_offset + skin,
+ *                 cell_size * size + grid_offset - skin], skin = boundary_skin_width.
+ *   2. collide  : _detect_collisions (:612-683) with grid::march_cells (include/fluid/data_structures/grid.h:140-209): from = the
+ *                 position before the move, up to three bounces, the bounce update in world units, then the skin push-out (:654-681).
+ *   3. transfer : _transfer_from_grid_pic (:447-461): velocity and type = lfa_sample_velocity at the new position.
+ * 1 and 2 read the stored velocity and the solid cells, 3 the grid the step's G2P read, so the result is what a placement inside
+ * the step would give. fp64, the reference's operations in its order: positions and velocities equal the oracle's advect,
+ * detect_collisions and PIC transfer bit for bit. Two deliberate differences, invisible on finite inputs: the march of a bounce
+ * takes at most nx + ny + nz + 3 face crossings, and a tracer whose moved position is not finite in every coordinate (a NaN
+ * velocity) is FROZEN: it keeps its position, is counted, and still takes a new velocity in 3.
+ * Single domain only: lfa_tracers_add on a handle with a slab decomposition, and lfa_dist_init_* on a handle that holds tracers,
+ * return LFA_E_UNSUPPORTED before anything is touched (tracers that migrate between ranks are the follow-up).
+ *   lfa_tracers_add            : appends n tracers in order; a tracer's index is its rank over all adds since the last clear. xyz
+ *                                double[3 n] (host), velocity double[3 n] or NULL: zeros. The total stays below 2^32. A non-finite
+ *                                position is LFA_E_INVALID, the message names the first bad index; checked on the host before
+ *                                anything is queued: nothing is added. Velocities may be anything. Positions outside the grid are
+ *                                accepted: their transfer gives +0.0 and type 0, the first move clamps them in. The type of a new
+ *                                tracer is 0 until its first transfer. A handle that never adds a tracer allocates nothing.
+ *   lfa_tracers_clear          : no tracers (the arrays are kept for the next add).     lfa_tracers_count: how many there are.
+ *   lfa_tracers_advect_collide : steps 1 + 2.     lfa_tracers_transfer: step 3.     lfa_tracers_step: 1 + 2 + 3 in one kernel, the
+ *                                same bits as the two stage calls. counts (or NULL: nothing is read back, the call does not wait):
+ *                                [0] tracers a march stopped at a solid cell or a wall, [1] tracers frozen.
+ *                                The three are queued on the handle's stream behind everything already there and write nothing but
+ *                                the tracer arrays. No tracers: LFA_OK, nothing launched. LFA_E_INVALID: dt not finite, cell_size unset.
+ *   lfa_tracers_download       : xyz double[3 n], velocity double[3 n], types uint8[n], each or NULL; n = lfa_tracers_count
+ *                                (LFA_E_INVALID otherwise).
+ *   lfa_tracers_time           : device milliseconds of the last tracer kernel (HIP events on the handle's stream). LFA_E_INVALID
+ *                                when none has run since the last clear. */
+int lfa_tracers_add(lfa_sim *s, const double *xyz, const double *velocity, uint64_t n);
+int lfa_tracers_clear(lfa_sim *s);
+int lfa_tracers_count(const lfa_sim *s, uint64_t *n);
+int lfa_tracers_advect_collide(lfa_sim *s, double dt);
+int lfa_tracers_transfer(lfa_sim *s);
+int lfa_tracers_step(lfa_sim *s, double dt, uint64_t counts[2]);
+int lfa_tracers_download(lfa_sim *s, double *xyz, double *velocity, uint8_t *types, uint64_t n);
+int lfa_tracers_time(lfa_sim *s, double *ms);
 /* Synthetic dam-break block [lo,hi) in cells, 8 jittered particles per cell, generated on the device; bit-identical
  * to libfluid_amd/scenes.py:seed_block. */
 int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_t seed);

@@ -98,6 +98,14 @@ SIGNATURES = {
     "lfa_sample_velocity": (_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
     "lfa_sample_velocity_collective": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64 * 3)]),
     "lfa_sample_velocity_time": (_int, [_vp, C.POINTER(_dbl)]),
+    "lfa_tracers_add": (_int, [_vp, _vp, _vp, _u64]),
+    "lfa_tracers_clear": (_int, [_vp]),
+    "lfa_tracers_count": (_int, [_vp, C.POINTER(_u64)]),
+    "lfa_tracers_advect_collide": (_int, [_vp, _dbl]),
+    "lfa_tracers_transfer": (_int, [_vp]),
+    "lfa_tracers_step": (_int, [_vp, _dbl, C.POINTER(_u64 * 2)]),
+    "lfa_tracers_download": (_int, [_vp, _vp, _vp, _vp, _u64]),
+    "lfa_tracers_time": (_int, [_vp, C.POINTER(_dbl)]),
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_seed_sphere": (_int, [_vp, _vp, _dbl, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
@@ -685,6 +693,53 @@ class Sim:
         """Device milliseconds of the kernel of the last sample_velocity() (lfa_sample_velocity_time)."""
         out = C.c_double(0.0)
         self._chk(self.lib.lfa_sample_velocity_time(self.h, C.byref(out)))
+        return out.value
+
+    # -- tracers: massless markers that move as PIC particles do and that no grid stage sees (csrc/tracers.hip) ----------------
+    def add_tracers(self, points, velocity=None):
+        """Appends tracers at world positions float64[n, 3] with velocities float64[n, 3] (None: zeros); a tracer's index is its
+        rank over all calls since the last clear_tracers(). A non-finite position raises and adds nothing (lfa_tracers_add)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        vel = None if velocity is None else np.ascontiguousarray(velocity, dtype=np.float64).reshape(-1, 3)
+        if vel is not None and vel.shape != pts.shape:
+            raise ValueError("velocity must have the shape of points")
+        self._chk(self.lib.lfa_tracers_add(self.h, _ptr(pts), None if vel is None else _ptr(vel), pts.shape[0]))
+
+    def clear_tracers(self):
+        self._chk(self.lib.lfa_tracers_clear(self.h))
+
+    def num_tracers(self):
+        n = _u64(0)
+        self._chk(self.lib.lfa_tracers_count(self.h, C.byref(n)))
+        return int(n.value)
+
+    def tracers_advect_collide(self, dt):
+        """position += velocity dt, clamped, then the collision handling against solid cells and walls (lfa_tracers_advect_collide)."""
+        self._chk(self.lib.lfa_tracers_advect_collide(self.h, float(dt)))
+
+    def tracers_transfer(self):
+        """velocity and type of every tracer = sample_velocity() at its position (lfa_tracers_transfer)."""
+        self._chk(self.lib.lfa_tracers_transfer(self.h))
+
+    def tracers_step(self, dt):
+        """(stopped, frozen): the two stages in one kernel, after time_step(dt) (lfa_tracers_step). stopped: tracers a march
+        stopped at a solid cell or a wall; frozen: tracers whose moved position was not finite and that kept their place."""
+        counts = (_u64 * 2)()
+        self._chk(self.lib.lfa_tracers_step(self.h, float(dt), C.byref(counts)))
+        return int(counts[0]), int(counts[1])
+
+    def tracers(self, types=False):
+        """pos float64[n, 3], vel float64[n, 3][, types uint8[n]] (lfa_tracers_download)."""
+        n = self.num_tracers()
+        pos, vel = np.empty((n, 3), dtype=np.float64), np.empty((n, 3), dtype=np.float64)
+        typ = np.empty(n, dtype=np.uint8) if types else None
+        self._chk(self.lib.lfa_tracers_download(self.h, _ptr(pos), _ptr(vel), None if typ is None else _ptr(typ), n))
+        return (pos, vel, typ) if types else (pos, vel)
+
+    def tracers_ms(self):
+        """Device milliseconds of the last tracer kernel (lfa_tracers_time)."""
+        out = C.c_double(0.0)
+        self._chk(self.lib.lfa_tracers_time(self.h, C.byref(out)))
         return out.value
 
     @property

@@ -289,6 +289,16 @@ struct lfa_sim {
 	hipEvent_t sample_ev[2] = {nullptr, nullptr};
 	bool sample_timed = false;
 
+	// tracers (tracers.hip): massless markers that move as PIC particles do and that no grid stage sees. One block from the pool: fp64
+	// x, y, z, vx, vy, vz [cap] each | the two count words of a step | the type bytes [cap]; nothing is allocated before the first
+	// lfa_tracers_add. The events sit around the last tracer kernel.
+	struct Tracers {
+		void *base = nullptr;
+		size_t n = 0, cap = 0;
+		hipEvent_t ev[2] = {nullptr, nullptr};
+		bool timed = false;
+	} tracers;
+
 	// timing
 	bool timing = false;
 	hipEvent_t ev[48];  // 0-9, 16-18: lfa_step_hot; 20-21: lfa_bench_kernel; 24-..: lfa_time_step (LFA_ST_* boundaries)
@@ -550,6 +560,7 @@ enum {
 	LFA_PIN_SOURCE_KEPT = 105,       // ... and those of them this rank keeps
 	LFA_PIN_SAMPLE_OWNED = 106,      // lfa_sample_velocity_collective: points this rank owns ...
 	LFA_PIN_SAMPLE_OUTSIDE = 107,    // ... and points outside the grid
+	LFA_PIN_TRACER_COUNTS = 108,     // lfa_tracers_step: tracers stopped in the march, and (109) tracers frozen
 };
 /// The scan, its total (left in *total_dev on the device) read back through h_pinned[slot]: one synchronisation of the stream.
 int lfa_scan_total(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev, int slot, size_t *total);

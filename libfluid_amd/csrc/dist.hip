@@ -977,6 +977,14 @@ struct ShmDist : lfa_dist {
 	}
 };
 
+/// Tracers live on a single domain (tracers.hip; migrating them between ranks is the follow-up): a handle that holds some takes no
+/// transport, and nothing of it is touched.
+static int refuse_with_tracers(lfa_sim *s, const char *who) {
+	if (s->tracers.n == 0) return LFA_OK;
+	return lfa_fail(s, LFA_E_UNSUPPORTED, "%s: the handle holds %zu tracers, which do not migrate between slabs yet (lfa_tracers_clear first)", who,
+	                s->tracers.n);
+}
+
 int attach(lfa_sim *s, lfa_dist *d, const int32_t *bounds) {
 	const int lo = bounds[d->rank], hi = bounds[d->rank + 1];
 	if (bounds[0] != 0 || bounds[d->nranks] != s->g.ntz || lo >= hi || lo < 0 || hi > s->g.ntz) {
@@ -1016,6 +1024,7 @@ extern "C" int lfa_dist_unique_id(void *id128) {
 
 extern "C" int lfa_dist_init_rccl(lfa_sim *s, int rank, int nranks, const void *id128, const int32_t *layer_bounds) {
 	if (!s || !id128 || !layer_bounds || rank < 0 || rank >= nranks) return LFA_E_INVALID;
+	LFA_TRY(refuse_with_tracers(s, "lfa_dist_init_rccl"));
 	if (!g_rccl.load()) return lfa_fail(s, LFA_E_UNSUPPORTED, "librccl could not be loaded");
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
@@ -1035,6 +1044,7 @@ extern "C" int lfa_dist_init_rccl(lfa_sim *s, int rank, int nranks, const void *
 
 extern "C" int lfa_dist_init_shm(lfa_sim *s, const char *name, int rank, int nranks, const int32_t *layer_bounds) {
 	if (!s || !name || name[0] != '/' || !layer_bounds || rank < 0 || rank >= nranks) return LFA_E_INVALID;
+	LFA_TRY(refuse_with_tracers(s, "lfa_dist_init_shm"));
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
 	ShmDist *d = new ShmDist();
@@ -1059,6 +1069,7 @@ extern "C" void lfa_dist_local_hub_destroy(lfa_hub *h) { delete h; }
 
 extern "C" int lfa_dist_init_local(lfa_sim *s, lfa_hub *h, int rank, const int32_t *layer_bounds) {
 	if (!s || !h || !layer_bounds || rank < 0 || rank >= h->n) return LFA_E_INVALID;
+	LFA_TRY(refuse_with_tracers(s, "lfa_dist_init_local"));
 	LFA_TRY(lfa_corr_commit(s));
 	LocalDist *d = new LocalDist();
 	d->rank = rank;

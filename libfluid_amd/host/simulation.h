@@ -112,6 +112,7 @@ namespace fluid_amd {
 			_host_stale = _grid_stale = false;  // the new handle holds nothing yet
 			_dev_stale = true;
 			_particles_handed_out = _grid_handed_out = false;
+			_n_tracers = 0;  // (they lived on the old handle)
 			_rehash_grid();
 		}
 
@@ -187,6 +188,21 @@ namespace fluid_amd {
 		std::vector<vec3d> sample_velocity(const std::vector<vec3d> &points, std::vector<unsigned char> *types = nullptr,
 		                                   std::size_t *n_outside = nullptr);
 
+		// Tracers (include/libfluid_amd.h, tracers): massless markers on the device that move as a PIC particle of the reference does -
+		// advected with their velocity, stopped by solid cells and walls, then given the grid's velocity at their new position - and
+		// that no stage of the simulation sees. They belong to the device handle: resize() drops them. Never throw: see last_status().
+		/// Appends tracers at world positions (`velocity`: null for zeros, else one per position); a tracer's index is its rank over
+		/// all calls since the last clear_tracers(). A non-finite position fails the call and adds nothing.
+		void add_tracers(const std::vector<vec3d> &positions, const std::vector<vec3d> *velocity = nullptr);
+		void clear_tracers();
+		std::size_t tracer_count() const { return _n_tracers; }
+		/// Position, and on request velocity and the cell type at the position, of every tracer.
+		void tracers(std::vector<vec3d> &pos, std::vector<vec3d> *vel = nullptr, std::vector<unsigned char> *types = nullptr);
+		/// time_step(dt) ends its device work with lfa_tracers_step(dt) - on the one-call path and on the staged path alike, before
+		/// post_grid_to_particle_transfer_callback -, so update() carries the tracers through every sub-step. Off: they stay where
+		/// they are. A simulation without tracers makes the calls it makes without this flag.
+		bool advance_tracers = true;
+
 		// callbacks, in calling order (include/fluid/simulation.h:150-175)
 		std::function<void(double)> pre_time_step_callback, post_advection_callback,
 			post_particle_to_grid_transfer_callback, post_gravity_callback;
@@ -248,6 +264,13 @@ namespace fluid_amd {
 		// look at the pressure / the grid velocities never notice; one that asks for particles() or changes the solid cells takes
 		// the correction back (lfa_correct_collide_undo: exact) and the stage runs where the reference has it.
 		bool _corr_in_flight = false;
+		std::size_t _n_tracers = 0;  // tracers on the handle (a simulation without any never calls a tracer entry point)
+		/// The end of a step's device work: the tracers take the step too. The grid the G2P read is on the device; an edit of the
+		/// grid that has not reached it yet is flushed first, as for sample_velocity().
+		bool _advance_tracers(double dt) {
+			if (!advance_tracers || _n_tracers == 0) return true;
+			return _flush_host_edits(true) && _ok(lfa_tracers_step(_dev, dt, nullptr));
+		}
 
 		/// 64-bit content hash of words [first_word, first_word + n_words) of every record of `stride_words` 64-bit words:
 		/// multiply-xorshift per word, chunks of 16 Ki records combined with their index. At most 8 OpenMP threads, and only for
@@ -619,6 +642,35 @@ namespace fluid_amd {
 		return out;
 	}
 
+	inline void simulation::add_tracers(const std::vector<vec3d> &positions, const std::vector<vec3d> *velocity) {
+		static_assert(sizeof(vec3d) == 24, "vec3d must be three packed doubles");
+		if (positions.empty() || !_device_current()) return;
+		if (velocity && velocity->size() != positions.size()) {
+			_status = LFA_E_INVALID;
+			_error = "add_tracers: one velocity per position";
+			return;
+		}
+		if (_ok(lfa_tracers_add(_dev, &positions[0].x, velocity ? &(*velocity)[0].x : nullptr, positions.size()))) _n_tracers += positions.size();
+	}
+	inline void simulation::clear_tracers() {
+		if (_n_tracers == 0 || !_dev) return;
+		if (_ok(lfa_tracers_clear(_dev))) _n_tracers = 0;
+	}
+	inline void simulation::tracers(std::vector<vec3d> &pos, std::vector<vec3d> *vel, std::vector<unsigned char> *types) {
+		pos.clear();
+		if (vel) vel->clear();
+		if (types) types->clear();
+		if (_n_tracers == 0 || _status < 0 || !_dev) return;
+		pos.resize(_n_tracers);
+		if (vel) vel->resize(_n_tracers);
+		if (types) types->resize(_n_tracers);
+		if (!_ok(lfa_tracers_download(_dev, &pos[0].x, vel ? &(*vel)[0].x : nullptr, types ? types->data() : nullptr, _n_tracers))) {
+			pos.clear();
+			if (vel) vel->clear();
+			if (types) types->clear();
+		}
+	}
+
 	inline void simulation::time_step(double dt) {
 		if (_status < 0) return;  // a latched device failure: see clear_status()
 		if (!_dev) { _status = LFA_E_NO_DEVICE; _error = "no device handle: resize() failed or was not called (there is no CPU fallback)"; return; }
@@ -631,7 +683,10 @@ namespace fluid_amd {
 		if (!_any_stage_callback()) {
 			// ---- the whole step in one call (src/simulation.cpp:43-125 incl. sources)
 			if (!_push_source_rng()) return;
-			if (_ok(lfa_time_step(_dev, dt, &residual, &iters))) _device_advanced();
+			if (_ok(lfa_time_step(_dev, dt, &residual, &iters))) {
+				_device_advanced();
+				_advance_tracers(dt);
+			}
 			_pull_source_rng();
 			return;
 		}
@@ -687,7 +742,7 @@ namespace fluid_amd {
 			ok = ok && stage(lfa_correct_collide(_dev, dt));
 		}
 		_corr_in_flight = false;
-		ok = ok && stage(lfa_extrapolate(_dev)) && stage(lfa_g2p(_dev));
+		ok = ok && stage(lfa_extrapolate(_dev)) && stage(lfa_g2p(_dev)) && _advance_tracers(dt);
 		_in_step = false;
 		if (ok && post_grid_to_particle_transfer_callback) {
 			post_grid_to_particle_transfer_callback(dt);
