@@ -84,8 +84,9 @@ def test_split_advect_then_collide(name):
 
 @pytest.mark.parametrize("name", mc.ISOLATED)
 def test_full_time_step(name):
-    """One lfa_time_step - the only way into k_advect_collide_count, whose waves take 8 x 64 particles behind an `i < n` guard
-    (n = 1, 64, 511, 513 here) - against the oracle's own time_step from the same state. The particles are at least 2 cells apart
+    """One lfa_time_step - the way into k_advect_collide_count, whose waves take 8 x 64 particles behind an `i < n` guard
+    (n = 1, 64, 511, 513 here; tests/test_gpu_binning_edges.py::test_time_step_counts_while_it_advects goes the same way with waves
+    of 512 distinct tiles and n around 2 048) - against the oracle's own time_step from the same state. The particles are at least 2 cells apart
     before and after the move, so the position correction moves none of them and the later stages add nothing to a position: the
     bar stays at 2e-5 h."""
     cloud = mc.build(name)
