@@ -1775,16 +1775,46 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		hipLaunchKernelGGL(k_check_rhs, dim3(1), dim3(256), 0, s->stream, (const double *)(P + PART_B2), pcg_grid_uncapped(s->n_ptiles), s->pcg_state);
 		LFA_LAUNCH_CHECK(s);
 	}
+	// Spray: tiles whose unknowns couple to nothing outside - exact, once; a no-op after the early-out. Their right-hand side is vr
+	// while vr is still b: ahead of the warm start's residual, which runs over every particle tile. (Behind it a closed tile was
+	// handed b - A p_guess and ended with A^-1 b - p_guess: about 0 for a droplet that lives from step to step.)
+	if (is_mg(s)) LFA_TRY(lfa_mg_solve_closed(s));
 	if (s->warm_started) {
-		// r = b - A p_guess: one SpMV and one subtraction before the first preconditioner application
+		// r = b - A p_guess: one SpMV and one subtraction before the first preconditioner application (on a closed tile p is the
+		// solution by now and r what its own solve left of b; no kernel of the iteration reads either)
 		hipLaunchKernelGGL(k_spmv<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, (const real *)v.p, v.q, scale, P + PART_ZS,
 		                   s->pcg_state);
 		hipLaunchKernelGGL((k_warm_residual<real, false>), dim3(G), dim3(256), 0, s->stream, tc, v.r, (const real *)v.q, v.p);
 		LFA_LAUNCH_CHECK(s);
 	}
 	s->pressure_epoch = 0;  // set to this solve's epoch once it has converged: a NaN or a capped solve is no guess for the next one
-	if (is_mg(s)) LFA_TRY(lfa_mg_solve_closed(s));  // (spray: tiles whose unknowns couple to nothing outside - exact, once; a no-op after the early-out)
-	if (!n_it && !dist) {  // nothing but closed tiles: no iteration
+	int *hstate = (int *)s->h_pinned;
+	auto read_state = [&]() -> int {
+		LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, 80, hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipStreamSynchronize(s->stream));
+		return LFA_OK;
+	};
+	// What k_check_rhs found, from the state words read back (single domain, where the host has not asked first): an error, 1: the
+	// right-hand side is zero and the solve is over, 0: neither.
+	auto rhs_verdict = [&]() -> int {
+		if (host_check) return 0;
+		if (hstate[3] == 2) {
+			s->pcg_poisoned = true;
+			return lfa_fail(s, LFA_E_NAN, "NaN in the divergence right-hand side");
+		}
+		s->last_rhs_zero = hstate[3] == 1;
+		if (hstate[3] != 1) return 0;
+		LFA_TRY(finish_zero_rhs());
+		return 1;
+	};
+	if (!n_it && !dist) {  // nothing but closed tiles: no iteration - the state words are read and acted on all the same
+		LFA_TRY(read_state());
+		const int zero = rhs_verdict();
+		if (zero) return zero < 0 ? zero : LFA_OK;
+		if (hstate[1]) {
+			s->pcg_poisoned = true;
+			return lfa_fail(s, LFA_E_NAN, "NaN in a closed tile's solve");
+		}
 		s->pressure_epoch = s->solve_epoch;
 		return LFA_OK;
 	}
@@ -1924,15 +1954,13 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	const int maxit = (int)s->prm.max_iterations;
 	const int chunk = 4;
 	int done = -1, nan = 0, i = 0;
-	int *hstate = (int *)s->h_pinned;
 	int aborted = 0;  // a kernel whose workgroups wait for each other gave a wait up (mg.hip: co_wait)
 	// Between chunks the host reads the state words. The fused forms test the residual of the chunk's last iteration first (k_pcg_a
 	// tests the one before it); the launch-per-operation form has tested it inside the iteration and only reads back. No kernel of
 	// that form waits for another, so `aborted` stays 0 there.
 	auto poll = [&]() -> int {
 		if (fused) LFA_TRY(test_residual(i - 1));
-		LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, 80, hipMemcpyDeviceToHost, s->stream));
-		LFA_HIP(s, hipStreamSynchronize(s->stream));
+		LFA_TRY(read_state());
 		done = hstate[0];
 		nan = hstate[1];
 		aborted = hstate[2];
@@ -1968,17 +1996,8 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		s->pressure_epoch = 0;  // (the pressure the aborted iterations left is no guess)
 		return solve_t<real>(s, dt, residual, iterations);
 	}
-	if (!host_check) {  // what k_check_rhs found
-		if (hstate[3] == 2) {
-			s->pcg_poisoned = true;
-			return lfa_fail(s, LFA_E_NAN, "NaN in the divergence right-hand side");
-		}
-		s->last_rhs_zero = hstate[3] == 1;
-		if (hstate[3] == 1) {
-			LFA_TRY(finish_zero_rhs());
-			return LFA_OK;
-		}
-	}
+	const int zero = rhs_verdict();
+	if (zero) return zero < 0 ? zero : LFA_OK;
 	const int iters = done >= 0 ? done : maxit;
 	double res = 0.0;
 	if (done > 0) {
