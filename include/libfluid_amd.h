@@ -472,6 +472,24 @@ int lfa_time_step(lfa_sim *s, double dt, double *residual, uint64_t *iterations)
  * Overlapped, [7] [8] [9] are spans on the correction's own stream and [4] [5] [6] [10] spans on the main one: each is
  * stretched by the other side's kernels sharing the device, and they no longer add up to [12]. */
 #define LFA_NUM_STEP_TIMERS 16
+enum { /* index of each entry, in the order above */
+	LFA_STEP_TIMER_ADVECT_COLLIDE,
+	LFA_STEP_TIMER_BIN,
+	LFA_STEP_TIMER_P2G,
+	LFA_STEP_TIMER_P2G_SCATTER_KERNEL,
+	LFA_STEP_TIMER_BUILD_SYSTEM,
+	LFA_STEP_TIMER_PCG_LOOP,
+	LFA_STEP_TIMER_APPLY_PRESSURE,
+	LFA_STEP_TIMER_CORRECT_CELL_INDEX,
+	LFA_STEP_TIMER_CORRECT_TILED_KERNEL,
+	LFA_STEP_TIMER_CORRECT_COLLIDE,
+	LFA_STEP_TIMER_EXTRAPOLATE,
+	LFA_STEP_TIMER_G2P,
+	LFA_STEP_TIMER_TIME_STEP,
+	LFA_STEP_TIMER_PCG_ITERATIONS,     /* a count, not a time */
+	LFA_STEP_TIMER_PCG_ITERATION_MEAN, /* a mean of times: PCG loop / iterations */
+	LFA_STEP_TIMER_OVERLAPPED          /* a flag, not a time */
+};
 int lfa_get_step_timings(lfa_sim *s, double ms[LFA_NUM_STEP_TIMERS]);
 /* lfa_time_step on a single domain runs the position correction (particle arrays only; simulation.cpp:99-106) on a second HIP
  * stream beside the pressure solve, the pressure gradient and the extrapolation (grid arrays only; :82-97, :119): forked after
@@ -693,6 +711,18 @@ int lfa_mesher_velocities_time(lfa_mesher *m, double *ms);
  * [0] hash/bin [1] P2G [2] gravity [3] build system [4] PCG loop [5] apply pressure [6] extrapolate [7] G2P
  * [8] P2G scatter kernel alone [9] mean PCG iteration (PCG loop / iterations). Enabled by lfa_enable_timing(s,1). */
 #define LFA_NUM_TIMERS 10
+enum { /* index of each entry, in the order above */
+	LFA_TIMER_BIN,
+	LFA_TIMER_P2G,
+	LFA_TIMER_GRAVITY,
+	LFA_TIMER_BUILD_SYSTEM,
+	LFA_TIMER_PCG_LOOP,
+	LFA_TIMER_APPLY_PRESSURE,
+	LFA_TIMER_EXTRAPOLATE,
+	LFA_TIMER_G2P,
+	LFA_TIMER_P2G_SCATTER_KERNEL,
+	LFA_TIMER_PCG_ITERATION_MEAN /* a mean of times: PCG loop / iterations */
+};
 int lfa_enable_timing(lfa_sim *s, int on);
 int lfa_get_timings(lfa_sim *s, double ms[LFA_NUM_TIMERS]);
 /* counts of the last step: [0] particles [1] unknowns (fluid cells) [2] tiles holding particles [3] tiles processed

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/libfluid_amd.h"
+#include "slots.h"
 
 // Every device allocation of the library goes through the process-wide block cache (pool.hip): the HIP names are redirected
 // here, after hip_runtime.h has declared the real ones. hipFree keeps its synchronising semantics unless the caller has
@@ -131,7 +132,7 @@ struct lfa_sim {
 	int n_halo[4] = {0, 0, 0, 0};
 	void *xbuf[4] = {nullptr, nullptr, nullptr, nullptr};  // send_lo, send_hi, recv_lo, recv_hi
 	size_t xcap[4] = {0, 0, 0, 0};
-	double *dist_red = nullptr;             // all-reduced scalars
+	double *dist_red = nullptr;             // all-reduced scalars (slots.h, LFA_DR_*)
 	size_t np_live = 0;
 	bool holes = false;  // slabs: leavers were invalidated in place since the last binning
 	size_t arrivals_at = 0, n_arrivals = 0;  // slabs: particles received since the last binning sit at [arrivals_at, arrivals_at + n_arrivals)
@@ -146,7 +147,7 @@ struct lfa_sim {
 	int n_ptiles = 0, n_dtiles = 0;
 	uint32_t *scan_tmp = nullptr;
 	size_t scan_tmp_len = 0;
-	uint32_t *h_pinned = nullptr;  // small pinned scratch for device->host scalars
+	uint32_t *h_pinned = nullptr;  // small pinned scratch for device->host scalars (slots.h, LFA_PIN_*)
 
 	// grid (blocked layout, ncp entries)
 	float *u = nullptr, *v = nullptr, *w = nullptr;
@@ -168,8 +169,8 @@ struct lfa_sim {
 	void *vs2 = nullptr;  // second search-direction buffer of the fused iteration (k_pcg_a reads one, writes the other)
 	size_t vec_elem = 0;  // element size the vectors are currently allocated for
 	double *partials = nullptr;  // reduction partials
-	int *pcg_state = nullptr;    // [0] done_iter  [1] nan flag
-	double *pcg_hist = nullptr;  // residual per iteration
+	int *pcg_state = nullptr;    // the device scalar block: slots.h, LFA_DW_*
+	double *pcg_hist = nullptr;  // residual per iteration (slots.h, LFA_HIST_*)
 	int *level_tiles = nullptr;  // ptile slots sorted by tile level (exact MIC)
 	std::vector<int> level_offsets;  // host: start of every level in level_tiles
 	// coarse levels of the multilevel preconditioner (pcg.hip): level 1 = one unknown per particle tile, stored as a
@@ -215,7 +216,7 @@ struct lfa_sim {
 	size_t vc_extent = 0;                   // records of pb[cur ^ 1] that vc_src may point at (slabs: arrivals append theirs behind)
 	bool vc_pending = false;
 	uint64_t stat_p2g_deferred = 0;         // LDS-binned P2G launches that read v, C through vc_src (lfa_get_solver_stats [6])
-	bool vmax2_valid = false;               // pcg_state[7] holds max |v|^2 of the particles (written by the last G2P, nothing has touched v since)
+	bool vmax2_valid = false;               // pcg_state[LFA_DW_VMAX2_BITS] holds max |v|^2 of the particles (written by the last G2P, nothing has touched v since)
 	// PIC / FLIP never change C (their P2G does not read it, their G2P does not write it; the hosts' particle records carry it
 	// through): instead of moving 36 bytes per particle with every binning, C is parked in a HOME array indexed by the particle
 	// id (stable; single domain) and only a download, a change to APIC or an attach to slabs brings it back (core.hip: c_home_*)
@@ -301,7 +302,7 @@ struct lfa_sim {
 
 	// timing
 	bool timing = false;
-	hipEvent_t ev[48];  // 0-9, 16-18: lfa_step_hot; 20-21: lfa_bench_kernel; 24-..: lfa_time_step (LFA_ST_* boundaries)
+	hipEvent_t ev[LFA_EV_COUNT];  // slots.h, LFA_EV_*
 	bool ev_created = false;
 	double ms[LFA_NUM_TIMERS] = {0};
 	double ms_next[LFA_NUM_STEP_TIMERS] = {0};  // lfa_get_step_timings
@@ -322,6 +323,25 @@ int lfa_fail(lfa_sim *s, int code, const char *fmt, ...);
 		if (rc_ < 0) return rc_; \
 	} while (0)
 #define LFA_LAUNCH_CHECK(s) LFA_HIP(s, hipGetLastError())
+
+// ---------------------------------------------------------------------------------------------------- timing
+/// Records event `id` (slots.h: LFA_EV_*) on the handle's current stream while timing is on.
+inline int lfa_ev_record(lfa_sim *s, int id) {
+	if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[id], s->stream));
+	return LFA_OK;
+}
+/// One row of a driver's timer table: ms[timer] = device time from event `from` to event `to`, both recorded.
+struct lfa_span {
+	int timer, from, to;
+};
+template <int N> inline int lfa_fill_spans(lfa_sim *s, const lfa_span (&rows)[N], double *ms) {
+	for (const lfa_span &r : rows) {
+		float f = 0.f;
+		LFA_HIP(s, hipEventElapsedTime(&f, s->ev[r.from], s->ev[r.to]));
+		ms[r.timer] = f;
+	}
+	return LFA_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------- indexing
 __host__ __device__ inline uint32_t blocked_index(const GridDims &g, int x, int y, int z) {
@@ -548,20 +568,6 @@ template <typename T> __device__ inline T wave_max(T v) {
 
 // generic exclusive scan of uint32 (scan.hip); out may alias in. Returns total in *total_dev (device) if non-null.
 int lfa_exclusive_scan_u32(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev);
-/// Words of lfa_sim::h_pinned that the seeding and source paths read a device count back through (core.hip: lfa_scan_total;
-/// seed.hip). The other files' claims: core.hip 0, 8-10, 20-29; pcg.hip 0 upwards (the solver's state) and 4-5; mg.hip 64
-/// upwards; grid_ops.hip and core.hip 100.
-enum {
-	LFA_PIN_SOURCE_TOTAL = 96,       // lfa_update_sources: particles the own entries create
-	LFA_PIN_SEED_ACCEPTED = 97,      // lfa_seed_box / _sphere: accepted candidates of the whole job ...
-	LFA_PIN_SEED_OWNED = 98,         // ... and those of them this rank keeps
-	LFA_PIN_RESIDENT = 99,           // lfa_particles_close_holes: resident records
-	LFA_PIN_SOURCE_TOTAL_ALL = 104,  // collective lfa_update_sources_rng: particles the whole job creates ...
-	LFA_PIN_SOURCE_KEPT = 105,       // ... and those of them this rank keeps
-	LFA_PIN_SAMPLE_OWNED = 106,      // lfa_sample_velocity_collective: points this rank owns ...
-	LFA_PIN_SAMPLE_OUTSIDE = 107,    // ... and points outside the grid
-	LFA_PIN_TRACER_COUNTS = 108,     // lfa_tracers_step: tracers stopped in the march, and (109) tracers frozen
-};
 /// The scan, its total (left in *total_dev on the device) read back through h_pinned[slot]: one synchronisation of the stream.
 int lfa_scan_total(lfa_sim *s, const uint32_t *in, uint32_t *out, size_t n, uint32_t *total_dev, int slot, size_t *total);
 
@@ -649,7 +655,6 @@ int lfa_dist_exchange_slices(lfa_sim *s, void *vec, int elem_bytes);  // elem_by
 /// layer lo_layer goes down, slice 7 of layer hi_layer - 1 goes up; they land in layers lo_layer - 1 and hi_layer.
 int lfa_dist_exchange_layer_slices(lfa_sim *s, void *vec, int elem_bytes, int tiles_per_layer, int lo_layer, int hi_layer);
 int lfa_dist_allreduce(lfa_sim *s, const double *partials, int n, int slot, bool is_max);  // result in dist_red[slot]
-#define LFA_DIST_ALPHA_OFF (64 + 2 * (3 * 32 + 1))  // dist_red: [0, 64) scalars | two gather buffers (<= 32 ranks) | alpha of the single-reduction CG
 double *lfa_dist_gather_buf(lfa_sim *s, int parity);  // [max per rank | sum per rank] of the last lfa_dist_gather_pair
 int lfa_dist_gather_pair(lfa_sim *s, const double *pmax, int n_max, const double *psum, int n_sum, int parity);
 int lfa_dist_gather_triple(lfa_sim *s, const double *pmax, int n_max, const double *psum, int n_sum, const double *psum2, int n_sum2,
@@ -669,7 +674,6 @@ inline int lfa_corr_commit(lfa_sim *s) {
 	s->corr_undo_valid = false;
 	return lfa_corr_join(s);
 }
-#define LFA_EV_CORRECT_END 30  // ev[] slot: end of the correction (B_CORRECT of lfa_time_step)
 /// Handles alive on a device (lfa_create +1, lfa_destroy -1). With more than one, the launches of kernels whose workgroups wait for
 /// each other are chained through events across the handles' streams (mg.hip: CoGate): two of them resident half each would wait
 /// for ever.

@@ -280,7 +280,7 @@ extern "C" int lfa_create(lfa_sim **out, uint64_t nx, uint64_t ny, uint64_t nz, 
 	if (lfa_stream_set *q = lfa_pool_take_set(device)) {
 		s->stream = q->stream; s->stream2 = q->stream2; s->stream3 = q->stream3;
 		s->ev_fork = q->ev_fork; s->ev_join = q->ev_join; s->ev_cfork = q->ev_cfork; s->ev_cjoin = q->ev_cjoin;
-		for (int i = 0; i < 48; ++i) s->ev[i] = q->ev[i];
+		for (int i = 0; i < LFA_EV_COUNT; ++i) s->ev[i] = q->ev[i];
 		s->ev_created = q->ev_created;
 		s->h_pinned = q->h_pinned;
 		delete q;
@@ -319,9 +319,9 @@ extern "C" int lfa_create(lfa_sim **out, uint64_t nx, uint64_t ny, uint64_t nz, 
 	chk(dev_alloc(s, &s->cell_count, s->ncp, true));
 	chk(dev_alloc(s, &s->abits, s->ncp, true));
 	chk(dev_alloc(s, &s->partials, 16384, true));  // >= PART_TOTAL (pcg.h)
-	chk(dev_alloc(s, &s->pcg_state, 32, true));  // [0] done [1] NaN [2] a wait was given up [3] 1: zero right-hand side, 2: NaN in it ... [16,17] the final residual (double)
-	chk(dev_alloc(s, &s->pcg_hist, 8192, true));  // [0,4096) residual history, [6144,..) coarse r2 hand-off
-	if (rc == LFA_OK && !s->h_pinned && hipHostMalloc((void **)&s->h_pinned, 4096, hipHostMallocDefault) != hipSuccess)
+	chk(dev_alloc(s, &s->pcg_state, LFA_DW_ALLOC, true));
+	chk(dev_alloc(s, &s->pcg_hist, LFA_HIST_COUNT, true));
+	if (rc == LFA_OK && !s->h_pinned && hipHostMalloc((void **)&s->h_pinned, LFA_PIN_BYTES, hipHostMallocDefault) != hipSuccess)
 		rc = lfa_fail(s, LFA_E_HIP, "hipHostMalloc failed");
 	if (rc == LFA_OK) {
 		hipLaunchKernelGGL(k_init_ctype, dim3((unsigned)((s->ncp + 255) / 256)), dim3(256), 0, s->stream, s->ctype,
@@ -382,7 +382,7 @@ extern "C" void lfa_destroy(lfa_sim *s) {
 		q->device = s->device;
 		q->stream = s->stream; q->stream2 = s->stream2; q->stream3 = s->stream3;
 		q->ev_fork = s->ev_fork; q->ev_join = s->ev_join; q->ev_cfork = s->ev_cfork; q->ev_cjoin = s->ev_cjoin;
-		for (int i = 0; i < 48; ++i) q->ev[i] = s->ev[i];
+		for (int i = 0; i < LFA_EV_COUNT; ++i) q->ev[i] = s->ev[i];
 		q->ev_created = s->ev_created;
 		q->h_pinned = s->h_pinned;
 		lfa_pool_park_set(q);
@@ -633,7 +633,7 @@ int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot) {
 	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((s->np_live + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->pb[s->cur].key,
 	                   s->np_live, s->rank);
 	LFA_LAUNCH_CHECK(s);
-	uint32_t *tot = (uint32_t *)(s->pcg_state + 5);
+	uint32_t *tot = (uint32_t *)(s->pcg_state + LFA_DW_SCAN_TOTAL);
 	LFA_TRY(lfa_exclusive_scan_u32(s, s->rank, s->rank, s->np_live, tot));
 	uint32_t h = 0;
 	LFA_HIP(s, hipMemcpyAsync(&h, tot, 4, hipMemcpyDeviceToHost, s->stream));
@@ -666,7 +666,7 @@ int lfa_particles_close_holes(lfa_sim *s, size_t n_rec) {
 	                   n_rec, s->rank);
 	LFA_LAUNCH_CHECK(s);
 	size_t n_dst = 0;
-	LFA_TRY(lfa_scan_total(s, s->rank, s->rank, n_rec, (uint32_t *)(s->pcg_state + 5), LFA_PIN_RESIDENT, &n_dst));
+	LFA_TRY(lfa_scan_total(s, s->rank, s->rank, n_rec, (uint32_t *)(s->pcg_state + LFA_DW_SCAN_TOTAL), LFA_PIN_RESIDENT, &n_dst));
 	// (unbinned, np counted the holes too - lfa_dist_migrate -: then the scan is what tells the resident count)
 	if (s->binned && n_dst != s->np) return lfa_fail(s, LFA_E_INVALID, "seeding: %u resident records but %zu expected", (uint32_t)n_dst, s->np);
 	hipLaunchKernelGGL(k_close_holes, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream, n_rec, s->pb[s->cur], s->pb[s->cur ^ 1],
@@ -1158,7 +1158,7 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 	}
 	// tile_start[0..nt] (exclusive scan; entry nt = number of live particles because tile_count[nt] == 0)
 	LFA_TRY(lfa_exclusive_scan_u32(s, s->tile_count, s->tile_start, (size_t)nt + 1, nullptr));
-	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 8, s->tile_start + nt, 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_NP_LIVE, s->tile_start + nt, 4, hipMemcpyDeviceToHost, s->stream));
 
 	// ---- particle tiles: owned ones from the counts, the neighbours' adjacent layers by message
 	hipLaunchKernelGGL(k_tile_flags, dim3((nt + 255) / 256), dim3(256), 0, s->stream, s->tile_count, s->tile_flag, nt);
@@ -1168,16 +1168,16 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 	LFA_LAUNCH_CHECK(s);
 	const bool one_sync = !s->dist;  // single domain: the tile lists are built without the host, their counts come back together
 	if (one_sync) {
-		uint32_t *tot = (uint32_t *)s->pcg_state + 8;  // [8] particle tiles, [9] processed tiles
+		uint32_t *tot = (uint32_t *)s->pcg_state + LFA_DW_N_PTILES;  // particle tiles, processed tiles
 		LFA_TRY(compact_tiles_async(s, s->tile_flag, 0, nt, s->ptiles_all, s->tile_pslot, tot));
 		LFA_HIP(s, hipMemsetAsync(s->tile_flag, 0, (size_t)(nt + 1) * 4, s->stream));
 		hipLaunchKernelGGL(k_dilate_slots, dim3((nt + 255) / 256), dim3(256), 0, s->stream, (const int *)s->tile_pslot, s->tile_flag, g);
 		LFA_LAUNCH_CHECK(s);
-		LFA_TRY(compact_tiles_async(s, s->tile_flag, 0, nt, s->dtiles, nullptr, tot + 1));
-		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 9, tot, 8, hipMemcpyDeviceToHost, s->stream));
+		LFA_TRY(compact_tiles_async(s, s->tile_flag, 0, nt, s->dtiles, nullptr, (uint32_t *)s->pcg_state + LFA_DW_N_DTILES));
+		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_N_PTILES, tot, 8, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		s->n_ptiles_all = (int)s->h_pinned[9];
-		s->n_dtiles = (int)s->h_pinned[10];
+		s->n_ptiles_all = (int)s->h_pinned[LFA_PIN_N_PTILES];
+		s->n_dtiles = (int)s->h_pinned[LFA_PIN_N_DTILES];
 		s->p_off = 0;
 		s->n_ptiles = s->n_ptiles_all;
 		s->n_own_first = s->n_own_last = s->n_ghost_lo = s->n_ghost_hi = 0;
@@ -1186,12 +1186,12 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 		// Slabs: the same without the host in between (round 3 read seven counts back one by one: the particle tiles, the layer
 		// marks, the processed tiles, four halo lists). Collectives (the flag exchanges) are stream operations; the halo lists
 		// have fixed regions of one tile layer each, so no count is needed to place them.
-		uint32_t *tot = (uint32_t *)s->pcg_state + 20;  // [0] particle tiles [1..4] scan at the layer marks [5] processed tiles [6..9] halo lists
+		uint32_t *tot = (uint32_t *)s->pcg_state + LFA_DW_SLAB;  // LFA_SLAB_*: particle tiles | scan at the layer marks | processed tiles | halo lists
 		LFA_TRY(compact_tiles_async(s, s->tile_flag, all_lo, all_hi, s->ptiles_all, s->tile_pslot, tot));
 		int marks[4] = {own_lo, own_lo + L < own_hi ? own_lo + L : own_hi, own_hi - L > own_lo ? own_hi - L : own_lo, own_hi};
-		int *didx = s->pcg_state + 12;
+		int *didx = s->pcg_state + LFA_DW_SLAB_MARKS;
 		LFA_HIP(s, hipMemcpyAsync(didx, marks, 16, hipMemcpyHostToDevice, s->stream));
-		hipLaunchKernelGGL(k_gather_u32, dim3(1), dim3(64), 0, s->stream, s->tile_scan, didx, 4, tot + 1);  // (before the next scan reuses tile_scan)
+		hipLaunchKernelGGL(k_gather_u32, dim3(1), dim3(64), 0, s->stream, s->tile_scan, didx, 4, tot + LFA_SLAB_MARK_SCAN);  // (before the next scan reuses tile_scan)
 		LFA_LAUNCH_CHECK(s);
 		LFA_HIP(s, hipMemsetAsync(s->tile_flag, 0, (size_t)(nt + 1) * 4, s->stream));
 		hipLaunchKernelGGL(k_dilate_slots, dim3((nt + 255) / 256), dim3(256), 0, s->stream, (const int *)s->tile_pslot, s->tile_flag, g);
@@ -1199,20 +1199,20 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 		if (own_lo > 0) LFA_HIP(s, hipMemsetAsync(s->tile_flag, 0, (size_t)own_lo * 4, s->stream));
 		if (own_hi < nt) LFA_HIP(s, hipMemsetAsync(s->tile_flag + own_hi, 0, (size_t)(nt - own_hi) * 4, s->stream));
 		LFA_TRY(lfa_dist_exchange_tile_layers_u32(s, s->tile_flag));
-		LFA_TRY(compact_tiles_async(s, s->tile_flag, own_lo, own_hi, s->dtiles, nullptr, tot + 5));
+		LFA_TRY(compact_tiles_async(s, s->tile_flag, own_lo, own_hi, s->dtiles, nullptr, tot + LFA_SLAB_N_DTILES));
 		{
 			const int hlo[4] = {s->slab_lo * L, (s->slab_hi - 1) * L, (s->slab_lo - 1) * L, s->slab_hi * L};
 			const bool on[4] = {lfa_has_lo(s), lfa_has_hi(s), lfa_has_lo(s), lfa_has_hi(s)};
-			LFA_HIP(s, hipMemsetAsync(tot + 6, 0, 16, s->stream));
+			LFA_HIP(s, hipMemsetAsync(tot + LFA_SLAB_N_HALO, 0, 16, s->stream));
 			for (int w = 0; w < 4; ++w)
-				if (on[w]) LFA_TRY(compact_tiles_async(s, s->tile_flag, hlo[w], hlo[w] + L, s->halo_tiles + (size_t)w * L, nullptr, tot + 6 + w));
+				if (on[w]) LFA_TRY(compact_tiles_async(s, s->tile_flag, hlo[w], hlo[w] + L, s->halo_tiles + (size_t)w * L, nullptr, tot + LFA_SLAB_N_HALO + w));
 		}
-		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 20, tot, 40, hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_SLAB, tot, LFA_SLAB_WORDS * 4, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		const uint32_t *h = s->h_pinned + 20;
-		s->n_ptiles_all = (int)h[0];
+		const uint32_t *h = s->h_pinned + LFA_PIN_SLAB;
+		s->n_ptiles_all = (int)h[LFA_SLAB_N_PTILES];
 		int vals[4];
-		for (int k = 0; k < 4; ++k) vals[k] = marks[k] >= all_hi ? s->n_ptiles_all : (int)h[1 + k];  // (the scan has no entry at the end of the range)
+		for (int k = 0; k < 4; ++k) vals[k] = marks[k] >= all_hi ? s->n_ptiles_all : (int)h[LFA_SLAB_MARK_SCAN + k];  // (the scan has no entry at the end of the range)
 		s->p_off = vals[0];
 		s->n_ptiles = vals[3] - vals[0];
 		s->n_own_first = vals[1] - vals[0];
@@ -1220,10 +1220,10 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 		s->n_ghost_lo = s->p_off;
 		s->n_ghost_hi = s->n_ptiles_all - vals[3];
 		s->ptiles = s->ptiles_all + s->p_off;
-		s->n_dtiles = (int)h[5];
-		for (int w = 0; w < 4; ++w) s->n_halo[w] = (int)h[6 + w];
+		s->n_dtiles = (int)h[LFA_SLAB_N_DTILES];
+		for (int w = 0; w < 4; ++w) s->n_halo[w] = (int)h[LFA_SLAB_N_HALO + w];
 	}
-	s->np_live = s->h_pinned[8];
+	s->np_live = s->h_pinned[LFA_PIN_NP_LIVE];
 	if (s->dist) s->np = s->np_live;  // particles migrate: the resident count is the live count
 	s->holes = false;
 	s->n_arrivals = 0;
@@ -1274,13 +1274,13 @@ int lfa_dist_build_halo_lists(lfa_sim *s, const uint32_t *flag, int *lists, int 
 	const int L = s->g.ntx * s->g.nty;
 	const int lo[4] = {s->slab_lo * L, (s->slab_hi - 1) * L, (s->slab_lo - 1) * L, s->slab_hi * L};
 	const bool on[4] = {lfa_has_lo(s), lfa_has_hi(s), lfa_has_lo(s), lfa_has_hi(s)};
-	uint32_t *tot = (uint32_t *)s->pcg_state + 26;  // (the binning's slots for its own four)
+	uint32_t *tot = (uint32_t *)s->pcg_state + LFA_DW_SLAB + LFA_SLAB_N_HALO;  // (the binning's slots for its own four)
 	LFA_HIP(s, hipMemsetAsync(tot, 0, 16, s->stream));
 	for (int w = 0; w < 4; ++w)
 		if (on[w]) LFA_TRY(compact_tiles_async(s, flag, lo[w], lo[w] + L, lists + (size_t)w * L, nullptr, tot + w));
-	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 26, tot, 16, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_SLAB + LFA_SLAB_N_HALO, tot, 16, hipMemcpyDeviceToHost, s->stream));
 	LFA_HIP(s, hipStreamSynchronize(s->stream));
-	for (int w = 0; w < 4; ++w) n[w] = (int)s->h_pinned[26 + w];
+	for (int w = 0; w < 4; ++w) n[w] = (int)s->h_pinned[LFA_PIN_SLAB + LFA_SLAB_N_HALO + w];
 	return LFA_OK;
 }
 
@@ -1303,10 +1303,10 @@ int lfa_number_unknowns(lfa_sim *s) {
 	hipLaunchKernelGGL(k_raw_unknown_flags, dim3((unsigned)((s->nc + 255) / 256)), dim3(256), 0, s->stream, s->g, s->nc,
 	                   s->cell_count, s->tile_flag, s->raw_scan, s->slab_lo * 8, s->slab_hi * 8);
 	LFA_LAUNCH_CHECK(s);
-	LFA_TRY(lfa_exclusive_scan_u32(s, s->raw_scan, s->raw_scan, s->nc, (uint32_t *)s->pcg_state + 10));
-	LFA_HIP(s, hipMemcpyAsync(s->h_pinned, (uint32_t *)s->pcg_state + 10, 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_TRY(lfa_exclusive_scan_u32(s, s->raw_scan, s->raw_scan, s->nc, (uint32_t *)s->pcg_state + LFA_DW_N_UNKNOWNS));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_N_UNKNOWNS, (uint32_t *)s->pcg_state + LFA_DW_N_UNKNOWNS, 4, hipMemcpyDeviceToHost, s->stream));
 	LFA_HIP(s, hipStreamSynchronize(s->stream));
-	s->n_unknowns = s->h_pinned[0];
+	s->n_unknowns = s->h_pinned[LFA_PIN_N_UNKNOWNS];
 	s->unknown_count_valid = true;
 	return LFA_OK;
 }
@@ -1390,7 +1390,7 @@ extern "C" int lfa_cfl(lfa_sim *s, double *out) {
 		// (grid_ops.hip: g2p_run): no pass over the particles, no copy of its own
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
 		float f;
-		memcpy(&f, s->h_pinned + 100, 4);
+		memcpy(&f, s->h_pinned + LFA_PIN_VMAX2_BITS, 4);
 		m = (double)f;
 	} else if (s->np_live) {
 		LFA_TRY(lfa_particles_materialize(s));

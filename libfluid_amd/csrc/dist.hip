@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(256) k_reduce_partials(const double *part, int
 /// reductions of k_reduce_partials): a SUM all-reduce of `out` then leaves every rank's pair on every rank (an all-gather
 /// that is exact in any order), and the consumers reduce n values instead of their per-workgroup partials.
 /// (`psum2`: a third list, summed like the second, for out[2 n + rank]: the single-reduction CG of slab runs; out is 3 n long)
-/// out[3 n] = 1 when a device-side wait of this rank's solve has been given up (pcg_state[2], sticky): summed over the ranks it
+/// out[3 n] = 1 when a device-side wait of this rank's solve has been given up (pcg_state[LFA_DW_GAVE_UP], sticky): summed over the ranks it
 /// tells EVERY rank at its next poll, so that all of them leave the loop and repeat the solve together (pcg.hip).
 __global__ void __launch_bounds__(256) k_gather_pair(const double *pmax, int n_max, const double *psum, int n_sum, const double *psum2,
                                                      int n_sum2, double *out, int n, int rank, const int *pcg_state) {
@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) k_gather_pair(const double *pmax, int n_m
 	}
 	for (int i = threadIdx.x; i < 3 * n; i += 256)
 		out[i] = i == rank ? lds[0][0] : (i == n + rank ? lds[1][0] : (i == 2 * n + rank ? lds[2][0] : 0.0));
-	if (threadIdx.x == 0) out[3 * n] = pcg_state && pcg_state[2] ? 1.0 : 0.0;
+	if (threadIdx.x == 0) out[3 * n] = pcg_state && pcg_state[LFA_DW_GAVE_UP] ? 1.0 : 0.0;
 }
 }  // namespace
 
@@ -329,7 +329,7 @@ int lfa_dist_allreduce(lfa_sim *s, const double *partials, int n, int slot, bool
 
 /// The signed max of `pmax` and the sum of `psum` of every rank in ONE collective: afterwards lfa_dist_gather_buf(s, parity)
 /// holds [max of rank 0 .. n-1 | sum of rank 0 .. n-1] on every rank.
-double *lfa_dist_gather_buf(lfa_sim *s, int parity) { return s->dist_red + 64 + (size_t)parity * (3 * s->dist->nranks + 1); }
+double *lfa_dist_gather_buf(lfa_sim *s, int parity) { return s->dist_red + LFA_DR_GATHER + (size_t)parity * (3 * s->dist->nranks + 1); }
 int lfa_dist_gather_pair(lfa_sim *s, const double *pmax, int n_max, const double *psum, int n_sum, int parity) {
 	return lfa_dist_gather_triple(s, pmax, n_max, psum, n_sum, nullptr, 0, parity);
 }
@@ -432,7 +432,7 @@ int lfa_dist_migrate(lfa_sim *s, bool vc_dead) {
 	// 0.12 ms per migration at C3 -: the pack kernel reads v, C where they are, the arrivals' go behind the other buffer's records)
 	(void)vc_dead;
 	const size_t n = s->binned ? s->np_live : s->np;
-	uint32_t *cnt = (uint32_t *)(s->dist_red + 32);  // [0,1] leaving lo/hi, [2,3] arriving from lo/hi
+	uint32_t *cnt = (uint32_t *)(s->dist_red + LFA_DR_MIGRATE_COUNTS);  // [0,1] leaving lo/hi, [2,3] arriving from lo/hi
 	LFA_HIP(s, hipMemsetAsync(cnt, 0, 16, s->stream));
 	const int tpl = s->g.ntx * s->g.nty;
 	const dim3 grid((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1));
@@ -505,7 +505,7 @@ int lfa_dist_exchange_ghost_particles(lfa_sim *s) {
 	for (int k = 0; k < 4; ++k)
 		LFA_HIP(s, hipMemcpyAsync(&hs[k], s->tile_start + marks[k], 4, hipMemcpyDeviceToHost, s->stream));
 	// ghost totals: sum of the received counts (scan over the ghost layer gives the per-tile starts as well)
-	uint32_t *tot = (uint32_t *)(s->dist_red + 40);
+	uint32_t *tot = (uint32_t *)(s->dist_red + LFA_DR_GHOST_TOTALS);
 	size_t n_g[2] = {0, 0};
 	uint32_t hg[2] = {0, 0};
 	if (lfa_has_lo(s)) LFA_TRY(lfa_exclusive_scan_u32(s, s->tile_count + own_lo - L, s->tile_scan + own_lo - L, (size_t)L, tot));
@@ -1007,7 +1007,7 @@ int attach(lfa_sim *s, lfa_dist *d, const int32_t *bounds) {
 	s->sources_built.clear();  // ... so entries flattened for another range (the whole domain, earlier bounds) are not "the same list"
 	s->grid_valid = false;
 	s->system_valid = false;
-	if (!s->dist_red) LFA_HIP(s, hipMalloc(&s->dist_red, (LFA_DIST_ALPHA_OFF + 8) * 8));  // scalars | 2 gather buffers of 3 x nranks + 1 | alpha of the single-reduction CG (2)
+	if (!s->dist_red) LFA_HIP(s, hipMalloc(&s->dist_red, LFA_DR_COUNT * 8));
 	if (!s->halo_tiles) LFA_HIP(s, hipMalloc(&s->halo_tiles, (size_t)4 * s->g.ntx * s->g.nty * 4));
 	return LFA_OK;
 }

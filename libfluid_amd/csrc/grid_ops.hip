@@ -606,14 +606,14 @@ static int g2p_run(lfa_sim *s, bool stale) {
 	const ParticleSoA &p = s->pb[s->cur];
 	if (s->prm.simulation_method == LFA_FLIP_BLEND && !s->uo) return lfa_fail(s, LFA_E_INVALID, "lfa_g2p: FLIP needs the old grid written by lfa_p2g");
 	// leaver list: the binning's rank array is free between two binnings; its counter sits behind the PCG state words
-	uint32_t *leavers = s->rank, *n_leavers = (uint32_t *)(s->pcg_state + 6);
+	uint32_t *leavers = s->rank, *n_leavers = (uint32_t *)(s->pcg_state + LFA_DW_N_LEAVERS);
 	// a deferred binning (lfa_sim::vc_pending): FLIP's old velocity still sits in the other buffer; PIC and APIC overwrite
 	// v, C without reading them. Either way the transfer completes the particle records in the binned order.
 	const ParticleSoA &pold = s->vc_pending ? s->pb[s->cur ^ 1] : s->pb[s->cur];
 	const uint32_t *from = s->vc_pending ? (const uint32_t *)s->vc_src : (const uint32_t *)nullptr;
 	if (stale) LFA_HIP(s, hipMemsetAsync(n_leavers, 0, 4, s->stream));
 	// the CFL reduction rides along: max |v|^2 of the velocities this transfer writes (every live particle gets one)
-	uint32_t *vmax2_bits = (uint32_t *)(s->pcg_state + 7);
+	uint32_t *vmax2_bits = (uint32_t *)(s->pcg_state + LFA_DW_VMAX2_BITS);
 	LFA_HIP(s, hipMemsetAsync(vmax2_bits, 0, 4, s->stream));
 	// (the STALE instantiation serves both cases: it allocates 62 VGPRs where the plain one gets 129 - 8 instead of 3 waves
 	// per SIMD; on freshly binned particles it finds no leavers)
@@ -639,7 +639,7 @@ static int g2p_run(lfa_sim *s, bool stale) {
 	s->vc_pending = false;
 	// max |v|^2 goes to the host behind the kernels that reduce it: lfa_cfl (the next step's dt) then only waits for the stream
 	// instead of queueing a copy of its own behind an idle device
-	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 100, s->pcg_state + 7, 4, hipMemcpyDeviceToHost, s->stream));
+	LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_VMAX2_BITS, vmax2_bits, 4, hipMemcpyDeviceToHost, s->stream));
 	s->vmax2_valid = true;  // every live particle has just got its velocity: the binned ones, the leavers and (slabs) the arrivals
 	return LFA_OK;
 }

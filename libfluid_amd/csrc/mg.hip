@@ -699,7 +699,7 @@ template <typename real> __device__ inline void coarsest_tile(const MgLv<real> &
 template <typename real>
 __global__ void __launch_bounds__(256) k_mg_presmooth(MgLv<real> L, const int *state) {
 	__shared__ real halo[PCG_WAVES][LFA_HALO_CELLS];
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	real *h = halo[wid];
 	for (int i = lane; i < LFA_HALO_CELLS; i += 64) h[i] = (real)0;  // the ring stays zero
@@ -717,7 +717,7 @@ k_mg_axpy_presmooth(const int *tiles, int n_tiles, const uint8_t *abits, real *p
 	const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	double m = -INFINITY;
 	bool nan = false;
-	if (state[0] < 0) {
+	if (state[LFA_DW_DONE] < 0) {
 		// software pipeline: the loads of the wave's next tile are in flight during the sweeps of the current one - and those of
 		// its first tile while the scalars of the previous kernel are reduced. The tile ids of the wave's next 64 slots sit in
 		// the lanes of one register (one load, v_readlane per tile): a load of the id in front of each tile's loads is a second,
@@ -807,7 +807,7 @@ k_mg_axpy_presmooth_cg(const int *tiles, int n_tiles, const uint8_t *abits, real
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	double m = -INFINITY;
 	bool nan = false;
-	bool run = state[0] < 0;
+	bool run = state[LFA_DW_DONE] < 0;
 	if (run && iter > 0) {  // every workgroup evaluates the rule on the same values, workgroup 0 records it
 		double rm = rmax_prev[0];
 		for (int i = 1; i < n_rmax; ++i) rm = nan_max(rm, rmax_prev[i]);
@@ -891,8 +891,8 @@ k_mg_axpy_presmooth_cg(const int *tiles, int n_tiles, const uint8_t *abits, real
 /// (src/pressure_solver.cpp:52-57: the reference leaves its loop BEFORE applying the preconditioner to a converged residual).
 /// Without it the rule is evaluated by the NEXT iteration's k_pcg_a, i.e. after a whole V-cycle whose result nobody reads: 0.19 of an
 /// iteration's 0.25 ms at C4, once per solve. Every workgroup reduces the same per-workgroup maxima (as k_pcg_a does), workgroup 0
-/// records the verdict exactly as k_pcg_a / k_check_converged would (hist[iter], state[0] = iter + 1); the kernels behind this one
-/// see state[0] and return.
+/// records the verdict exactly as k_pcg_a / k_check_converged would (hist[iter], state[LFA_DW_DONE] = iter + 1); the kernels behind this one
+/// see state[LFA_DW_DONE] and return.
 struct MgStop {
 	const double *part_rmax;  // null: no test here (slabs: the maximum is another collective; levels >= 1)
 	int n_part, iter;
@@ -904,7 +904,7 @@ template <typename real>
 __global__ void __launch_bounds__(256) k_mg_residual_restrict(MgLv<real> L, GridDims gc, real *b_coarse, const int *state, MgStop stop) {
 	__shared__ real halo[PCG_WAVES][LFA_HALO_CELLS];
 	__shared__ double red[4];
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	real *h = halo[wid];
 	const int stride = gridDim.x * PCG_WAVES;
@@ -990,7 +990,7 @@ k_mg_prolong_postsmooth(MgLv<real> L, GridDims gc, const real *e, real inv_scale
 	const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	real *h = halo[wid];
 	double acc = 0.0;
-	const bool run = state[0] < 0;
+	const bool run = state[LFA_DW_DONE] < 0;
 	if (run) {
 		// The body of prolong_postsmooth_tile as a software pipeline: every load of the wave's next tile (column, ring, the
 		// parents' corrections) is in flight while the current tile is swept in LDS.
@@ -1258,20 +1258,20 @@ template <typename real, typename MEM> __device__ inline void cp_coarsest_tile(C
 template <typename real>
 __global__ void __launch_bounds__(256) k_mg_presmooth_cp(MgLv<real> L, int inner, const int *state) {
 	__shared__ CpTile<real> S;
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	for (int slot = blockIdx.x; slot < L.n_tiles; slot += gridDim.x) cp_presmooth_tile<real, MemPlain>(S, L, slot, inner);
 }
 template <typename real>
 __global__ void __launch_bounds__(256) k_mg_residual_restrict_cp(MgLv<real> L, GridDims gc, real *b_coarse, const int *state) {
 	__shared__ CpTile<real> S;
 	__shared__ real R[512];
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	for (int slot = blockIdx.x; slot < L.n_tiles; slot += gridDim.x) cp_residual_restrict_tile<real, MemPlain>(S, R, L, gc, b_coarse, slot);
 }
 template <typename real>
 __global__ void __launch_bounds__(256) k_mg_prolong_postsmooth_cp(MgLv<real> L, GridDims gc, const real *e, int inner, const int *state) {
 	__shared__ CpTile<real> S;
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	for (int slot = blockIdx.x; slot < L.n_tiles; slot += gridDim.x) cp_prolong_postsmooth_tile<real, MemPlain>(S, L, gc, e, slot, inner);
 }
 
@@ -1313,7 +1313,7 @@ template <typename real> struct MgCo {
 	unsigned tag;
 	unsigned long long *xq[MG_MAX_LEVELS];  // TAGGED hand-off: per level [x | b | y], each the level's padded grid of {tag, value} words
 	size_t ncp[MG_MAX_LEVELS];
-	int *abort;                  // pcg_state + 2: raised by a workgroup whose wait has passed CO_TIMEOUT_TICKS; every waiter checks it
+	int *abort;                  // pcg_state + LFA_DW_GAVE_UP: raised by a workgroup whose wait has passed CO_TIMEOUT_TICKS; every waiter checks it
 	int fault;                   // LFA_MG_CO_FAULT=n (tests): workgroup n - 1 never raises its first flag
 };
 
@@ -1369,9 +1369,9 @@ __device__ inline void co_wait(const unsigned *flag, const int *dep, int n, unsi
 				}
 			}
 			if (bad) {
-				// (for the record: abort_word[16] = 0x100 "a wait ran out" | the waiter's XCC id)
+				// (for the record: abort_word[LFA_DW_GAVE_UP_REASON - LFA_DW_GAVE_UP] = 0x100 "a wait ran out" | the waiter's XCC id)
 				if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-					abort_word[16] = 0x100 | (int)co_xcc_id();
+					abort_word[LFA_DW_GAVE_UP_REASON - LFA_DW_GAVE_UP] = 0x100 | (int)co_xcc_id();
 				__hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			}
 		}
@@ -1484,7 +1484,7 @@ template <int N> __device__ inline void co_get(const unsigned long long *const (
 		do {
 			co_backoff(tries);
 			if (co_poll_expired(tries, t0, abort_word)) {
-				if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) abort_word[16] = 0x400 | (int)co_xcc_id();
+				if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) abort_word[LFA_DW_GAVE_UP_REASON - LFA_DW_GAVE_UP] = 0x400 | (int)co_xcc_id();
 				__hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				break;
 			}
@@ -1563,8 +1563,8 @@ __device__ inline bool co_static(const MgCo<real> &P, const CoThread &T, CoLevel
 	int nbv = 0;
 	if (t < 8 * nlev && P.first + (t >> 3) <= lmax) nbv = P.lv[P.first + (t >> 3)].nbr[(size_t)T.wg * MG_NBR_STRIDE + (t & 7)];
 	if (state) {
-		const int st0 = state[0];
-		if (st0 >= 0 || state[2] != 0) return false;  // converged (or a wait was given up): the launches queued behind are no-ops
+		const int st0 = state[LFA_DW_DONE];
+		if (st0 >= 0 || state[LFA_DW_GAVE_UP] != 0) return false;  // converged (or a wait was given up): the launches queued behind are no-ops
 	}
 	if (t < 8 * nlev) st[t >> 3].nb[t & 7] = nbv;
 	for (int l = P.first; l <= lmax; ++l) {
@@ -1868,7 +1868,7 @@ __global__ void __launch_bounds__(256) k_mg_coarse(MgCo<real> P, const int *stat
 	if (TAGGED && n_top) {
 		const int b = (int)blockIdx.x;
 		if (b < 2 * n_top || b >= 2 * n_top + W) {
-			if (state[0] >= 0 || state[2] != 0) return;  // converged, or a wait was given up
+			if (state[LFA_DW_DONE] >= 0 || state[LFA_DW_GAVE_UP] != 0) return;  // converged, or a wait was given up
 			CpTile<real> &S = *(CpTile<real> *)co_smem;
 			real *R = (real *)(&S + 1);
 			const MgLv<real> &L = P.lv[P.top];
@@ -2017,7 +2017,7 @@ __global__ void __launch_bounds__(MG_TAIL_WAVES * 64) k_mg_tail(MgTail<real> T, 
 	__shared__ real halo[MG_TAIL_WAVES][LFA_HALO_CELLS];
 	__shared__ real cb[MG_CHAIN_MAX][512], cx[MG_CHAIN_MAX][512], cy[MG_CHAIN_MAX][512];  // level arrays of the single-tile chain
 	__shared__ uint8_t cab[MG_CHAIN_MAX][512];
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	real *h = halo[wid];
 	for (int l = T.first; l < T.chain; ++l) {
@@ -2286,7 +2286,7 @@ template <typename real> static int mg_setup_device_lists(lfa_sim *s, MgSetup &U
 		hipLaunchKernelGGL(k_mg_small_lists, dim3(1), dim3(1024), 0, s->stream, SP, M.counts);
 		LFA_LAUNCH_CHECK(s);
 	}
-	uint32_t *hc = s->h_pinned + 64;
+	uint32_t *hc = s->h_pinned + LFA_PIN_MG_COUNTS;
 	if (nl > 1) {
 		LFA_HIP(s, hipMemcpyAsync(hc, M.counts, (size_t)nl * 4, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
@@ -2769,7 +2769,7 @@ template <typename real> static int mg_launch_coarse(lfa_sim *s, int top, void (
 			C.xq[top] = M.lv[top].xq;
 			C.ncp[top] = M.lv[top].ncp;
 		}
-		C.abort = s->pcg_state + 2;
+		C.abort = s->pcg_state + LFA_DW_GAVE_UP;
 		C.fault = s->knobs.mg_co_fault;
 		// one workgroup per tile of its first level: every workgroup owns one tile slot on every level it reaches
 		const int W = std::max(1, M.lv[tail].n_tiles) + 3 * C.top_wgs;
@@ -2965,7 +2965,7 @@ __global__ void __launch_bounds__(256)
 k_mg_solve_closed(const int *ptiles, int n_ptiles, const uint8_t *closed, const uint8_t *abits, const real *b, real *p, real inv_scale,
                   real tol, int *state) {
 	__shared__ real halo[PCG_WAVES][LFA_HALO_CELLS];
-	if (state[0] >= 0) return;  // (the zero right-hand side's early-out: p stays 0 like the reference's, src/pressure_solver.cpp:33-35)
+	if (state[LFA_DW_DONE] >= 0) return;  // (the zero right-hand side's early-out: p stays 0 like the reference's, src/pressure_solver.cpp:33-35)
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	real *h = halo[wid];
 	for (int slot = blockIdx.x * PCG_WAVES + wid; slot < n_ptiles; slot += gridDim.x * PCG_WAVES) {
@@ -3019,7 +3019,7 @@ k_mg_solve_closed(const int *ptiles, int n_ptiles, const uint8_t *closed, const 
 			if (rmax != rmax) bad = true;
 			else if (rmax <= stop) break;
 		}
-		if (bad && lane == 0) state[1] = 1;
+		if (bad && lane == 0) state[LFA_DW_NAN] = 1;
 #pragma unroll
 		for (int zz = 0; zz < 8; ++zz) p[base + zz * 64 + lane] = h[halo_at(lx, ly, zz)] * inv_scale;
 		MG_FENCE();

@@ -436,7 +436,7 @@ int lfa_p2g_run(lfa_sim *s, bool fuse_gravity, double dt) {
 	// a deferred binning: v, C come from the other buffer through vc_src
 	const ParticleSoA &p = s->pb[s->cur], &pvc = s->vc_pending ? s->pb[s->cur ^ 1] : s->pb[s->cur];
 	const uint32_t *from = s->vc_pending ? (const uint32_t *)s->vc_src : (const uint32_t *)nullptr;
-	if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[16], s->stream));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_SCATTER_BEGIN));
 	if (binned) {
 		if ((size_t)s->n_ptiles_all > s->stage_tiles) {
 			if (s->stage) LFA_HIP(s, hipFree(s->stage));
@@ -469,7 +469,7 @@ int lfa_p2g_run(lfa_sim *s, bool fuse_gravity, double dt) {
 			LFA_LAUNCH_CHECK(s);
 		}
 	}
-	if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[17], s->stream));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_SCATTER_END));
 	FinalizeParams fp;
 	fp.method = method;
 	fp.fuse_gravity = fuse_gravity ? 1 : 0;

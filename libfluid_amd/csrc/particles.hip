@@ -1371,9 +1371,9 @@ static int update_sources(lfa_sim *s, uint64_t *n_seeded, uint64_t *rng_state, i
 	uint64_t id_base = s->np_live, total_all = total;
 	if (s->dist) {
 		const int nr = s->dist->nranks, me = s->dist->rank;
-		double hv[32] = {0};
+		double hv[LFA_DR_MAX_RANKS] = {0};
 		hv[me] = (double)total;
-		double *dv = s->dist_red + 16;  // (slots 0-5 belong to the solve)
+		double *dv = s->dist_red + LFA_DR_SOURCE_TOTALS;
 		LFA_HIP(s, hipMemcpyAsync(dv, hv, (size_t)nr * 8, hipMemcpyHostToDevice, s->stream));
 		LFA_TRY(s->dist->allreduce_buf(s, dv, (size_t)nr, LFA_RED_F64, false));
 		LFA_HIP(s, hipMemcpyAsync(hv, dv, (size_t)nr * 8, hipMemcpyDeviceToHost, s->stream));
@@ -1597,7 +1597,7 @@ static int correct_build_index(lfa_sim *s, bool exchange = true) {
 	const int n_index = s->dist ? s->n_ptiles_all : s->n_ptiles;
 	const int grid = n_index < 16384 ? (n_index > 0 ? n_index : 1) : 16384;
 	ParticleSoA &cur = s->pb[s->cur];
-	if (s->timing && n) LFA_HIP(s, hipEventRecord(s->ev[40], s->stream));
+	if (n) LFA_TRY(lfa_ev_record(s, LFA_EV_CORR_BEGIN));
 	hipLaunchKernelGGL(k_build_fine_index, dim3(grid), dim3(FIDX_THREADS), 0, s->stream, s->dist ? s->ptiles_all : s->ptiles, n_index, cur.key,
 	                   cur.t[0], cur.t[1], cur.t[2], s->tile_start, s->tile_count, s->fine_start, correction_scratch(s), s->pb[s->cur ^ 1].key);
 	LFA_LAUNCH_CHECK(s);
@@ -1630,12 +1630,12 @@ static int correct_apply(lfa_sim *s, double dt, bool migrate = true, bool with_c
 			// every neighbour position comes from the records of the index built above (the OLD positions), so the new ones are
 			// written in place; the fallback pass below takes its particles' old state from the records and the copy of the keys
 			// the index kernel has left in the other buffer
-			if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[41], s->stream));
+			LFA_TRY(lfa_ev_record(s, LFA_EV_CORR_INDEXED));
 			hipLaunchKernelGGL((k_correct_fine<FINE_CAP, false>), dim3(g2), dim3(CORR_THREADS), 0, s->stream, s->ptiles, s->n_ptiles, cur.key,
 			                   cur.t[0], cur.t[1], cur.t[2], s->g, s->solid, s->tile_count, s->fine_start, (const float4 *)spos, mpc, ovf,
 			                   (const uint8_t *)s->tile_clear, (const uint32_t *)nullptr);
 			LFA_LAUNCH_CHECK(s);
-			if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[42], s->stream));
+			LFA_TRY(lfa_ev_record(s, LFA_EV_CORR_TILED));
 			// (a workgroup per CU and a few more: they return at once unless something is flagged)
 			hipLaunchKernelGGL((k_correct_fine<FINE_CAP_BIG, true>), dim3(std::min(CORR_BIG_SLICES * g2, 2048)), dim3(CORR_THREADS_BIG), 0, s->stream, s->ptiles,
 			                   s->n_ptiles, cur.key, cur.t[0], cur.t[1], cur.t[2], s->g, s->solid, s->tile_count, s->fine_start,
@@ -1706,7 +1706,7 @@ static int correct_begin(lfa_sim *s, double dt, bool slab_exchanged) {
 	int rc = correct_build_index(s, false);
 	if (rc == LFA_OK) rc = correct_apply(s, dt, false);
 	s->stream = main_stream;
-	const hipError_t e1 = s->timing ? hipEventRecord(s->ev[LFA_EV_CORRECT_END], s->stream3) : hipSuccess;
+	const hipError_t e1 = s->timing ? hipEventRecord(s->ev[LFA_EV_STEP_CORRECT], s->stream3) : hipSuccess;
 	// the join event is recorded whatever happened: the main stream waits for it before it touches particles again
 	const hipError_t e2 = hipEventRecord(s->ev_cjoin, s->stream3);
 	s->corr_in_flight = true;
@@ -1771,24 +1771,16 @@ extern "C" int lfa_time_step(lfa_sim *s, double dt, double *residual, uint64_t *
 		return lfa_fail(s, LFA_E_UNSUPPORTED, "lfa_time_step: fluid sources that draw from the pcg32 (lfa_set_source_rng) on a slab decomposition");
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
-	const bool tm = s->timing;
-	// stage boundaries: ev[24 + k]
-	enum { B_START = 24, B_ADVECT, B_BIN, B_P2G, B_SOLVE, B_APPLY, B_CORRECT, B_EXTRAP, B_G2P, B_JOIN };
-	static_assert(B_CORRECT == LFA_EV_CORRECT_END, "event slot of the end of the correction");
-	auto rec = [&](int id) -> int {
-		if (tm) LFA_HIP(s, hipEventRecord(s->ev[id], s->stream));
-		return LFA_OK;
-	};
-	LFA_TRY(rec(B_START));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_START));
 	LFA_TRY(advect_collide(s, dt, true));
-	LFA_TRY(rec(B_ADVECT));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_ADVECT));
 	{
 		const bool counted = s->counts_fresh;
 		s->counts_fresh = false;
 		LFA_TRY(lfa_hash_particles_impl(s, counted));
 	}
 	if (!s->sources.empty()) LFA_TRY(lfa_update_sources(s, nullptr));  // _update_sources + hash_particles (:63-64)
-	LFA_TRY(rec(B_BIN));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_BIN));
 	// The correction reads and writes particle positions only, the pressure solve / gradient / extrapolation grid arrays only:
 	// the two run side by side (the solve is a chain of short launch- and HBM-bound kernels, the correction one long VALU-bound
 	// one); the correction's stream has the lower priority. (Starting its cell index already beside the P2G - it only reads the
@@ -1797,7 +1789,7 @@ extern "C" int lfa_time_step(lfa_sim *s, double dt, double *residual, uint64_t *
 	// rank - a rank without particles included -, or the ranks would issue their collectives in different orders).
 	const bool overlap = s->overlap_correction && (s->dist || s->np_live);
 	LFA_TRY(lfa_p2g_run(s, true, dt));
-	LFA_TRY(rec(B_P2G));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_P2G));
 	if (overlap) {
 		if (s->dist) LFA_TRY(lfa_dist_exchange_ghost_particles(s));
 		LFA_TRY(correct_begin(s, dt, true));
@@ -1808,68 +1800,65 @@ extern "C" int lfa_time_step(lfa_sim *s, double dt, double *residual, uint64_t *
 	auto grid_stages = [&]() -> int {
 		rc = lfa_pcg_solve(s, dt, &res, &it);
 		if (rc < 0) return rc;
-		LFA_TRY(rec(B_SOLVE));
+		LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_SOLVE));
 		LFA_TRY(lfa_apply_pressure(s, dt));
-		LFA_TRY(rec(B_APPLY));
+		LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_APPLY));
 		if (!overlap) {
 			LFA_TRY(lfa_correct_collide(s, dt));
-			LFA_TRY(rec(B_CORRECT));
+			LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_CORRECT));
 		}
 		LFA_TRY(lfa_extrapolate(s));  // the valid set is the one of the P2G-time hash, like the reference (:119)
-		return rec(B_EXTRAP);
+		return lfa_ev_record(s, LFA_EV_STEP_EXTRAP);
 	};
 	const int rc_grid = grid_stages();
 	// joined whatever happened in between: nothing that follows on the main stream may race with the correction
 	if (overlap) LFA_TRY(lfa_corr_join(s));
 	if (rc_grid < 0) return rc_grid;
 	if (overlap && s->dist) LFA_TRY(lfa_dist_migrate(s, true));
-	LFA_TRY(rec(B_JOIN));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_JOIN));
 	// The G2P gathers per tile. The particles keep the order of the P2G-time binning and the few whose corrected position left
 	// their tile take the global-gather path (lfa_g2p_stale); like after lfa_advect_collide the order is stale afterwards and
 	// the next step re-bins. Slabs: the same - particles that went to a neighbour rank carry an invalid key (skipped), the ones
 	// that arrived sit behind the binned ones and join the leaver list. (Round 2 re-binned here: +18 % on a one-rank slab run.)
 	LFA_TRY(lfa_g2p_stale(s));
-	if (tm) {
-		LFA_TRY(rec(B_G2P));
-		LFA_HIP(s, hipEventSynchronize(s->ev[B_G2P]));
-		auto span = [&](int a, int b, double &out) -> int {
-			float ms = 0.f;
-			LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[a], s->ev[b]));
-			out = ms;
-			return LFA_OK;
-		};
+	if (s->timing) {
+		LFA_TRY(lfa_ev_record(s, LFA_EV_STEP_G2P));
+		LFA_HIP(s, hipEventSynchronize(s->ev[LFA_EV_STEP_G2P]));
 		double *m = s->ms_next;
-		const bool solved = it || s->n_ptiles;  // ev[18] (end of the system build) is recorded inside a non-trivial solve
-		LFA_TRY(span(B_START, B_ADVECT, m[0]));
-		LFA_TRY(span(B_ADVECT, B_BIN, m[1]));
-		LFA_TRY(span(B_BIN, B_P2G, m[2]));
-		LFA_TRY(span(16, 17, m[3]));
-		if (solved) {
-			LFA_TRY(span(B_P2G, 18, m[4]));
-			LFA_TRY(span(18, B_SOLVE, m[5]));
-		} else {
-			LFA_TRY(span(B_P2G, B_SOLVE, m[4]));
-			m[5] = 0.0;
+		static const lfa_span spans[] = {
+			{LFA_STEP_TIMER_ADVECT_COLLIDE, LFA_EV_STEP_START, LFA_EV_STEP_ADVECT},
+			{LFA_STEP_TIMER_BIN, LFA_EV_STEP_ADVECT, LFA_EV_STEP_BIN},
+			{LFA_STEP_TIMER_P2G, LFA_EV_STEP_BIN, LFA_EV_STEP_P2G},
+			{LFA_STEP_TIMER_P2G_SCATTER_KERNEL, LFA_EV_SCATTER_BEGIN, LFA_EV_SCATTER_END},
+			{LFA_STEP_TIMER_BUILD_SYSTEM, LFA_EV_STEP_P2G, LFA_EV_STEP_SOLVE},
+			{LFA_STEP_TIMER_APPLY_PRESSURE, LFA_EV_STEP_SOLVE, LFA_EV_STEP_APPLY},
+			{LFA_STEP_TIMER_G2P, LFA_EV_STEP_JOIN, LFA_EV_STEP_G2P},
+			{LFA_STEP_TIMER_TIME_STEP, LFA_EV_STEP_START, LFA_EV_STEP_G2P},
+		};
+		LFA_TRY(lfa_fill_spans(s, spans, m));
+		m[LFA_STEP_TIMER_PCG_LOOP] = 0.0;
+		if (it || s->n_ptiles) {  // a solve ran: the split is at the end of the system build, recorded inside it
+			static const lfa_span split[] = {{LFA_STEP_TIMER_BUILD_SYSTEM, LFA_EV_STEP_P2G, LFA_EV_SYSTEM_BUILT},
+			                                 {LFA_STEP_TIMER_PCG_LOOP, LFA_EV_SYSTEM_BUILT, LFA_EV_STEP_SOLVE}};
+			LFA_TRY(lfa_fill_spans(s, split, m));
 		}
-		LFA_TRY(span(B_SOLVE, B_APPLY, m[6]));
+		m[LFA_STEP_TIMER_CORRECT_CELL_INDEX] = m[LFA_STEP_TIMER_CORRECT_TILED_KERNEL] = m[LFA_STEP_TIMER_CORRECT_COLLIDE] = 0.0;
 		if (s->np_live) {
-			LFA_TRY(span(40, 41, m[7]));
-			LFA_TRY(span(41, 42, m[8]));
-		} else {
-			m[7] = m[8] = 0.0;
+			static const lfa_span corr[] = {{LFA_STEP_TIMER_CORRECT_CELL_INDEX, LFA_EV_CORR_BEGIN, LFA_EV_CORR_INDEXED},
+			                                {LFA_STEP_TIMER_CORRECT_TILED_KERNEL, LFA_EV_CORR_INDEXED, LFA_EV_CORR_TILED}};
+			LFA_TRY(lfa_fill_spans(s, corr, m));
 		}
-		// overlapped: the correction's own span on its stream (its kernels share the device with the solve's)
-		if (overlap && !s->np_live) {
-			m[9] = 0.0;
-		} else {
-			LFA_TRY(span(overlap ? 40 : B_APPLY, B_CORRECT, m[9]));
+		// overlapped: the correction's own span on its stream (its kernels share the device with the solve's), and the
+		// extrapolation follows the pressure gradient; back to back: the correction sits between the two
+		if (!overlap || s->np_live) {
+			const lfa_span whole[] = {{LFA_STEP_TIMER_CORRECT_COLLIDE, overlap ? LFA_EV_CORR_BEGIN : LFA_EV_STEP_APPLY, LFA_EV_STEP_CORRECT}};
+			LFA_TRY(lfa_fill_spans(s, whole, m));
 		}
-		LFA_TRY(span(overlap ? B_APPLY : B_CORRECT, B_EXTRAP, m[10]));
-		LFA_TRY(span(B_JOIN, B_G2P, m[11]));
-		m[15] = overlap ? 1.0 : 0.0;
-		LFA_TRY(span(B_START, B_G2P, m[12]));
-		m[13] = (double)it;
-		m[14] = it ? m[5] / (double)it : 0.0;
+		const lfa_span extrap[] = {{LFA_STEP_TIMER_EXTRAPOLATE, overlap ? LFA_EV_STEP_APPLY : LFA_EV_STEP_CORRECT, LFA_EV_STEP_EXTRAP}};
+		LFA_TRY(lfa_fill_spans(s, extrap, m));
+		m[LFA_STEP_TIMER_PCG_ITERATIONS] = (double)it;
+		m[LFA_STEP_TIMER_PCG_ITERATION_MEAN] = it ? m[LFA_STEP_TIMER_PCG_LOOP] / (double)it : 0.0;
+		m[LFA_STEP_TIMER_OVERLAPPED] = overlap ? 1.0 : 0.0;
 	}
 	if (residual) *residual = res;
 	if (iterations) *iterations = it;

@@ -87,9 +87,9 @@ __device__ inline bool verdict_stops(double rmax, double tol) { return rmax != r
 __device__ inline void record_verdict(int *state, double *hist, int slot, double rmax, bool stops) {
 	hist[slot] = rmax;
 	if (stops) {
-		if (rmax != rmax) state[1] = 1;
-		*(double *)(state + 16) = rmax;
-		state[0] = slot + 1;
+		if (rmax != rmax) state[LFA_DW_NAN] = 1;
+		*(double *)(state + LFA_DW_RESIDUAL) = rmax;
+		state[LFA_DW_DONE] = slot + 1;
 	}
 }
 

@@ -111,7 +111,7 @@ k_spmv(TileCtx tc, const uint8_t *abits, const real *s, real *z, real scale, dou
 	__shared__ double red[4];
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	double acc = 0.0;
-	if (state[0] < 0) {
+	if (state[LFA_DW_DONE] < 0) {
 		real *h = halo[wid];
 		for (int slot = blockIdx.x * PCG_WAVES + wid; slot < tc.n_ptiles; slot += gridDim.x * PCG_WAVES) {
 			const int tile = tc.ptiles[slot];
@@ -159,7 +159,7 @@ k_axpy_max(TileCtx tc, const uint8_t *abits, Vecs<real> v, const double *part_si
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	double m = -INFINITY;
 	bool nan = false;
-	if (state[0] < 0) {
+	if (state[LFA_DW_DONE] < 0) {
 		const double sigma = reduce_partials_sum(part_sigma, n_sigma, lds);
 		const double zs = reduce_partials_sum(part_zs, n_part, lds);
 		const real alpha = (real)(sigma / zs);
@@ -417,7 +417,7 @@ __global__ void __launch_bounds__(WAVES * 64)
 k_coarse_all(const int *l1_tiles, int n_l1, CoarseFields<real> c, real scale, const real *a2inv, real *x2,
              double *part_sigma_extra, const int *state) {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	coarse_block<real, WAVES>(smem, l1_tiles, n_l1, c, scale, a2inv, x2, part_sigma_extra);
 }
 
@@ -453,7 +453,7 @@ k_mic_apply(TileCtx tc, const int *slots, int n_slots, const uint8_t *abits, Vec
 	const int nblk = EMBED ? (int)gridDim.x - PCG_COARSE_BLOCKS : (int)gridDim.x,
 	          blk = EMBED ? (int)blockIdx.x - PCG_COARSE_BLOCKS : (int)blockIdx.x;
 	if (EMBED && blockIdx.x < PCG_COARSE_BLOCKS) {
-		if (state[0] < 0)
+		if (state[LFA_DW_DONE] < 0)
 			coarse_block<real, PCG_WAVES>(lds_raw, ca.l1_tiles, ca.n_l1, cf, scale, (const real *)ca.a2inv, (real *)ca.x2,
 			                              part_sigma + nblk, (int)blockIdx.x, PCG_COARSE_BLOCKS, ca.xchg, ca.ticket);
 		return;
@@ -464,7 +464,7 @@ k_mic_apply(TileCtx tc, const int *slots, int n_slots, const uint8_t *abits, Vec
 	real *P = (real *)lds_raw + (size_t)(2 * PCG_WAVES + wid) * LFA_TILE_CELLS;
 	uint8_t *A = (uint8_t *)((real *)lds_raw + (size_t)3 * PCG_WAVES * LFA_TILE_CELLS) + (size_t)wid * LFA_TILE_CELLS;
 	double acc = 0.0;
-	if (state[0] < 0) {
+	if (state[LFA_DW_DONE] < 0) {
 		for (int k = blk * PCG_WAVES + wid; k < n_slots; k += nblk * PCG_WAVES) {
 			const int slot = slots ? slots[k] : k;
 			const int tile = tc.ptiles[slot];
@@ -579,7 +579,7 @@ k_dot_zr(TileCtx tc, Vecs<real> v, double *part_sigma, const int *state) {
 	__shared__ double red[4];
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	double acc = 0.0;
-	if (state[0] < 0) {
+	if (state[LFA_DW_DONE] < 0) {
 		for (int slot = blockIdx.x * PCG_WAVES + wid; slot < tc.n_ptiles; slot += gridDim.x * PCG_WAVES) {
 			const size_t base = (size_t)tc.ptiles[slot] * LFA_TILE_CELLS;
 #pragma unroll
@@ -590,15 +590,15 @@ k_dot_zr(TileCtx tc, Vecs<real> v, double *part_sigma, const int *state) {
 }
 
 /// Stopping rule of pressure_solver::solve (src/pressure_solver.cpp:54-58): signed max(r) < tolerance ends the solve
-/// with iteration count i+1. One workgroup; later kernels of the stream see state[0] >= 0 and do nothing.
+/// with iteration count i+1. One workgroup; later kernels of the stream see state[LFA_DW_DONE] >= 0 and do nothing.
 __global__ void __launch_bounds__(256)
 k_check_converged(const double *part_rmax, int n_part, double tol, int iter, int *state, double *hist, const double *gave_up = nullptr) {
 	__shared__ double lds[256];
 	// slabs: how many ranks gave a device-side wait up (the last word of the gather, dist.hip: k_gather_pair). The retreat is
 	// collective: a rank that leaves the loop alone would redo the system build and its collectives while its peers carry on
 	// with the V-cycle's, and the transport sequences would no longer pair up.
-	if (gave_up && threadIdx.x == 0 && *gave_up > 0.0 && state[2] == 0) state[2] = 1;
-	if (state[0] >= 0) return;
+	if (gave_up && threadIdx.x == 0 && *gave_up > 0.0 && state[LFA_DW_GAVE_UP] == 0) state[LFA_DW_GAVE_UP] = 1;
+	if (state[LFA_DW_DONE] >= 0) return;
 	const double rmax = reduce_partials_max(part_rmax, n_part, lds);
 	if (threadIdx.x == 0) record_verdict(state, hist, iter, rmax, verdict_stops(rmax, tol));
 }
@@ -606,19 +606,19 @@ k_check_converged(const double *part_rmax, int n_part, double tol, int iter, int
 /// The early-out of pressure_solver::solve (src/pressure_solver.cpp:28-35: sum b^2 < 1e-6 returns p = 0, residual 0, 0 iterations)
 /// evaluated on the device: the solve is marked done before its first kernel - which, like every kernel of the loop, does nothing
 /// then - and the host learns it at its first poll instead of draining the GPU for one number ahead of every solve.
-/// state[3] = 1: zero right-hand side, 2: NaN in it.
+/// state[LFA_DW_RHS] = 1: zero right-hand side, 2: NaN in it.
 __global__ void __launch_bounds__(256) k_check_rhs(const double *part_b2, int n_part, int *state) {
 	__shared__ double lds[4];
 	const double tot = reduce_partials_sum(part_b2, n_part, lds);
 	if (threadIdx.x == 0) {
 		if (tot != tot) {
-			state[3] = 2;
-			state[1] = 1;
-			state[0] = 0;
+			state[LFA_DW_RHS] = 2;
+			state[LFA_DW_NAN] = 1;
+			state[LFA_DW_DONE] = 0;
 		} else if (tot < 1e-6) {
-			state[3] = 1;
-			*(double *)(state + 16) = 0.0;
-			state[0] = 0;
+			state[LFA_DW_RHS] = 1;
+			*(double *)(state + LFA_DW_RESIDUAL) = 0.0;
+			state[LFA_DW_DONE] = 0;
 		}
 	}
 }
@@ -631,7 +631,7 @@ k_update_s(TileCtx tc, Vecs<real> v, const double *part_sig_new, const double *p
            const int *state, const uint8_t *abits, const real *coarse_x, const int *slot_l1, const real *coarse_x2,
            const int *l1_l2) {
 	__shared__ double lds[256];
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	real beta = (real)0;
 	if (!first) {
 		const double sn = reduce_partials_sum(part_sig_new, n_part, lds);
@@ -813,7 +813,7 @@ k_coarse_top(const int *l1_tiles, int n_l1, CoarseFields<real> c, const real *a2
              double *part_sigma_extra, const int *state) {
 	__shared__ double red[4];
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	for (int row = threadIdx.x; row < n_l1; row += 256) {
 		double acc = 0.0;
 		for (int k = 0; k < n_l1; ++k) acc += (double)a2inv[(size_t)row * n_l1 + k] * (double)r2[k];
@@ -963,7 +963,7 @@ k_ghost_face_rows(TileCtx tc, int n_lo, int hi_slot0, int n_hi, const uint8_t *a
 	__shared__ double red[4];
 	const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, lx = lane & 7, ly = lane >> 3;
 	double acc = 0.0;
-	if (state[0] < 0) {
+	if (state[LFA_DW_DONE] < 0) {
 		for (int w = blockIdx.x * PCG_WAVES + wid; w < n_lo + n_hi; w += gridDim.x * PCG_WAVES) {
 			const bool lo = w < n_lo;
 			const int slot = lo ? w : hi_slot0 + (w - n_lo), zs = lo ? 0 : 7;
@@ -1043,7 +1043,7 @@ k_pcg_b(const int *__restrict__ ptiles, int n_ptiles, const uint8_t *__restrict_
 		}
 	};
 	if (!coarse_wg && slot < n_ptiles) load_tile(slot);
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	double sigma, zs;
 	reduce_partials_sum2(part_sigma_old, n_sigma, part_zs, n_zs, red, sigma, zs);
 	const real alpha = (real)(sigma / zs);
@@ -1191,7 +1191,7 @@ k_pcg_a(int n_ptiles, const int *__restrict__ nbr, const uint8_t *__restrict__ a
 		}
 	};
 	if (slot < n_ptiles) load_tile(slot);  // in flight while the scalars of the previous kernel are reduced
-	if (state[0] >= 0) return;
+	if (state[LFA_DW_DONE] >= 0) return;
 	if (iter > 0) {
 		// stopping rule of pressure_solver::solve (src/pressure_solver.cpp:54-58) on the residual of iteration iter-1;
 		// every workgroup evaluates it on the same partials, workgroup 0 records it
@@ -1353,7 +1353,7 @@ template <typename real> static CoarseFields<real> make_coarse(lfa_sim *s, real 
 }
 /// the coarse levels inside a launch of k_mic_apply / k_pcg_b (EMBED): what their PCG_COARSE_BLOCKS workgroups need beside the fields
 static CoarseArgs embedded_coarse(lfa_sim *s) {
-	return CoarseArgs{s->l1_tiles, s->n_l1tiles, s->a2inv, s->c_x2, (double *)s->pcg_hist + 6144, (unsigned *)(s->pcg_state + 4)};
+	return CoarseArgs{s->l1_tiles, s->n_l1tiles, s->a2inv, s->c_x2, (double *)s->pcg_hist + LFA_HIST_COARSE, (unsigned *)(s->pcg_state + LFA_DW_COARSE_TICKET)};
 }
 
 /// Dense SPD inverse by Cholesky (n2 is the number of 64^3-cell aggregates that hold fluid: tens, at most 512).
@@ -1713,7 +1713,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	if (s->dist && s->prm.precond == LFA_PRECOND_MIC0_EXACT)
 		return lfa_fail(s, LFA_E_UNSUPPORTED, "the exact (hyperplane) MIC(0) schedule is single-GPU only");
 	LFA_TRY(build_system_t<real>(s, dt));
-	if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[18], s->stream));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_SYSTEM_BUILT));
 	// The host polls the solver state between chunks of iterations; iterations launched after convergence are no-ops but
 	// still cost their launches (~40 us each). The count barely changes from step to step, so the first chunk is as long
 	// as the previous solve, the following ones short. (Identical on every rank of a slab run: the scalars are all-reduced.)
@@ -1733,8 +1733,8 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	const real scale = (real)s->a_scale;
 	double *P = s->partials;
 	const bool dist = s->dist != nullptr;
-	int init_state[4] = {-1, 0, 0, 0};
-	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, 16, hipMemcpyHostToDevice, s->stream));
+	int init_state[LFA_DW_SOLVER_WORDS] = {-1, 0, 0, 0};
+	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, sizeof init_state, hipMemcpyHostToDevice, s->stream));
 	// how a solve whose right-hand side is zero ends, whether the host or the device found it so
 	auto finish_zero_rhs = [&]() -> int {
 		if (s->warm_started) {  // the reference returns p = 0 here (src/pressure_solver.cpp:33-35), not the guess
@@ -1753,8 +1753,8 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		double tot = 0.0;
 		if (dist) {
 			if (!s->n_ptiles) LFA_HIP(s, hipMemsetAsync(P + PART_B2, 0, 8, s->stream));
-			LFA_TRY(lfa_dist_allreduce(s, P + PART_B2, pcg_grid_uncapped(s->n_ptiles), 0, false));
-			LFA_HIP(s, hipMemcpyAsync(&tot, s->dist_red, 8, hipMemcpyDeviceToHost, s->stream));
+			LFA_TRY(lfa_dist_allreduce(s, P + PART_B2, pcg_grid_uncapped(s->n_ptiles), LFA_DR_B2, false));
+			LFA_HIP(s, hipMemcpyAsync(&tot, s->dist_red + LFA_DR_B2, 8, hipMemcpyDeviceToHost, s->stream));
 			LFA_HIP(s, hipStreamSynchronize(s->stream));
 		} else {
 			std::vector<double> hb(pcg_grid_uncapped(s->n_ptiles));
@@ -1788,9 +1788,9 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		LFA_LAUNCH_CHECK(s);
 	}
 	s->pressure_epoch = 0;  // set to this solve's epoch once it has converged: a NaN or a capped solve is no guess for the next one
-	int *hstate = (int *)s->h_pinned;
+	int *hstate = (int *)(s->h_pinned + LFA_PIN_STATE);
 	auto read_state = [&]() -> int {
-		LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, 80, hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipMemcpyAsync(hstate, s->pcg_state, LFA_DW_READBACK_WORDS * 4, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
 		return LFA_OK;
 	};
@@ -1798,12 +1798,12 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	// right-hand side is zero and the solve is over, 0: neither.
 	auto rhs_verdict = [&]() -> int {
 		if (host_check) return 0;
-		if (hstate[3] == 2) {
+		if (hstate[LFA_DW_RHS] == 2) {
 			s->pcg_poisoned = true;
 			return lfa_fail(s, LFA_E_NAN, "NaN in the divergence right-hand side");
 		}
-		s->last_rhs_zero = hstate[3] == 1;
-		if (hstate[3] != 1) return 0;
+		s->last_rhs_zero = hstate[LFA_DW_RHS] == 1;
+		if (hstate[LFA_DW_RHS] != 1) return 0;
 		LFA_TRY(finish_zero_rhs());
 		return 1;
 	};
@@ -1811,7 +1811,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		LFA_TRY(read_state());
 		const int zero = rhs_verdict();
 		if (zero) return zero < 0 ? zero : LFA_OK;
-		if (hstate[1]) {
+		if (hstate[LFA_DW_NAN]) {
 			s->pcg_poisoned = true;
 			return lfa_fail(s, LFA_E_NAN, "NaN in a closed tile's solve");
 		}
@@ -1823,12 +1823,12 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	// with slabs - the all-reduced value
 	double *red = s->dist_red;
 	auto sig_part = [&](int parity) { return P + (parity ? PART_SIG1 : PART_SIG0); };
-	auto sig_src = [&](int parity) { return dist ? red + 3 + parity : sig_part(parity); };
+	auto sig_src = [&](int parity) { return dist ? red + LFA_DR_SIGMA + parity : sig_part(parity); };
 	const int n_sig = dist ? 1 : NS, n_zs = dist ? 1 : G;
 	const real *cx = is_ml(s) ? (const real *)s->c_x : (const real *)nullptr;
 	// z = M^-1 r ; s = z ; sigma = z.r
 	LFA_TRY(mic_apply<real>(s, P + PART_SIG0));
-	if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_SIG0, NS, 3, false));
+	if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_SIG0, NS, LFA_DR_SIGMA, false));
 	// fused iteration (k_pcg_a / k_pcg_b): tile-local MIC(0) with or without the coarse levels, single domain or slabs
 	// (with the multigrid preconditioner the second kernel is the AXPY/pre-smoothing kernel followed by the V-cycle, mg.hip)
 	const bool fused = (is_mg(s) || s->prm.pcg_fused) && s->prm.precond != LFA_PRECOND_MIC0_EXACT && (s->n_ptiles == 0 || s->nbr_table);
@@ -1872,7 +1872,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	auto step_cg1 = [&](int i) -> int {
 		const int po = i & 1, pn = po ^ 1;
 		const double *cur = lfa_dist_gather_buf(s, po), *old = lfa_dist_gather_buf(s, pn);
-		LFA_TRY(lfa_mg_axpy_apply_cg<real>(s, cur + nr, nr, old + nr, nr, cur + 2 * nr, nr, cur, nr, i, s->dist_red + LFA_DIST_ALPHA_OFF,
+		LFA_TRY(lfa_mg_axpy_apply_cg<real>(s, cur + nr, nr, old + nr, nr, cur + 2 * nr, nr, cur, nr, i, s->dist_red + LFA_DR_ALPHA,
 		                                   P + PART_RMAX, sig_part(pn)));
 		return step_a(i + 1, P + PART_RMAX, GB, sig_part(pn), NSB);
 	};
@@ -1882,10 +1882,10 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		// wrote NS sigma partials, k_pcg_b writes NSB), or - with slabs - the all-reduced values
 		// slabs: sigma_k (k >= 1) and the signed max of the residual it belongs to arrive together, one value per rank
 		// (lfa_dist_gather_pair, parity k & 1); sigma_0 of the application before the loop is the all-reduced scalar
-		const double *sig_po = !dist ? sig_part(po) : (i == 0 ? red + 3 : lfa_dist_gather_buf(s, po) + nr);
-		const double *sig_pn = !dist ? sig_part(pn) : (i <= 1 ? red + 3 : lfa_dist_gather_buf(s, pn) + nr);
+		const double *sig_po = !dist ? sig_part(po) : (i == 0 ? red + LFA_DR_SIGMA : lfa_dist_gather_buf(s, po) + nr);
+		const double *sig_pn = !dist ? sig_part(pn) : (i <= 1 ? red + LFA_DR_SIGMA : lfa_dist_gather_buf(s, pn) + nr);
 		const int n_sig_po = dist ? (i == 0 ? 1 : nr) : (i == 0 ? NS : NSB), n_sig_pn = dist ? (i <= 1 ? 1 : nr) : (i <= 1 ? NS : NSB);
-		const double *rmax_prev = !dist ? P + PART_RMAX : (i == 0 ? red + 2 : lfa_dist_gather_buf(s, po));
+		const double *rmax_prev = !dist ? P + PART_RMAX : (i == 0 ? red + LFA_DR_RMAX : lfa_dist_gather_buf(s, po));
 		const int n_rmax_prev = dist ? (i == 0 ? 1 : nr) : GB;
 		launch_pcg_a<real>(i == 0, is_ml(s), GA, s->stream, n_it, (const int *)s->nbr_table, (const uint8_t *)s->abits,
 		                   (const real *)v.z, (const real *)sbuf[po], sbuf[pn], v.q, scale, sig_po, n_sig_po, sig_pn, n_sig_pn,
@@ -1896,9 +1896,9 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 			// the new search direction across the slab faces, then the rows of q that needed it
 			LFA_TRY(lfa_dist_exchange_slices(s, sbuf[pn], (int)sizeof(real)));
 			LFA_TRY(ghost_face_rows<real>(s, faces, sbuf[pn], cas, face_parts));
-			LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G_ZS, 1, false));
+			LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G_ZS, LFA_DR_ZS, false));
 		}
-		const double *zs_src = dist ? red + 1 : P + PART_ZS;
+		const double *zs_src = dist ? red + LFA_DR_ZS : P + PART_ZS;
 		const int n_zs_src = dist ? 1 : GA;
 		if (is_mg(s)) {
 			// (single domain: the V-cycle's first kernel tests the residual this AXPY produces - the reference does not
@@ -1924,7 +1924,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 			n = nr;
 			gave_up = rmax + 3 * nr;
 		} else if (dist) {
-			rmax = red + 2;
+			rmax = red + LFA_DR_RMAX;
 			n = 1;
 		}
 		hipLaunchKernelGGL(k_check_converged, dim3(1), dim3(256), 0, s->stream, rmax, n, s->prm.tolerance, it, s->pcg_state, s->pcg_hist, gave_up);
@@ -1937,15 +1937,15 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		hipLaunchKernelGGL(k_spmv<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, (const real *)v.s, v.z, scale,
 		                   P + PART_ZS, s->pcg_state);
 		LFA_LAUNCH_CHECK(s);
-		if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G, 1, false));
+		if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_ZS, G, LFA_DR_ZS, false));
 		hipLaunchKernelGGL(k_axpy_max<real>, dim3(G), dim3(256), 0, s->stream, tc, s->abits, v, sig_src(po), n_sig,
-		                   dist ? red + 1 : P + PART_ZS, n_zs, P + PART_RMAX, s->pcg_state,
+		                   dist ? red + LFA_DR_ZS : P + PART_ZS, n_zs, P + PART_RMAX, s->pcg_state,
 		                   is_ml(s) ? (real *)s->c_r : (real *)nullptr, (const int *)s->slot_l1);
 		LFA_LAUNCH_CHECK(s);
-		if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_RMAX, G, 2, true));
+		if (dist) LFA_TRY(lfa_dist_allreduce(s, P + PART_RMAX, G, LFA_DR_RMAX, true));
 		LFA_TRY(test_residual(i));
 		LFA_TRY(mic_apply<real>(s, sig_part(pn), true));
-		if (dist) LFA_TRY(lfa_dist_allreduce(s, sig_part(pn), NS, 3 + pn, false));
+		if (dist) LFA_TRY(lfa_dist_allreduce(s, sig_part(pn), NS, LFA_DR_SIGMA + pn, false));
 		hipLaunchKernelGGL(k_update_s<real>, dim3(G), dim3(256), 0, s->stream, tc, v, sig_src(pn), sig_src(po), n_sig, 0,
 		                   s->pcg_state, s->abits, cx, (const int *)s->slot_l1, (const real *)s->c_x2, (const int *)s->l1_l2);
 		LFA_LAUNCH_CHECK(s);
@@ -1961,9 +1961,9 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	auto poll = [&]() -> int {
 		if (fused) LFA_TRY(test_residual(i - 1));
 		LFA_TRY(read_state());
-		done = hstate[0];
-		nan = hstate[1];
-		aborted = hstate[2];
+		done = hstate[LFA_DW_DONE];
+		nan = hstate[LFA_DW_NAN];
+		aborted = hstate[LFA_DW_GAVE_UP];
 		return LFA_OK;
 	};
 	const int form = cg1 ? 2 : fused ? 1 : 0;  // the iteration step: chosen here, once
@@ -1988,7 +1988,7 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 		// a fault). Whatever the iterations after it computed is void. This handle stops using the kernels that wait and the solve
 		// is repeated from the right-hand side on the launch-per-phase path - once: that path waits for nothing.
 		if (s->co_disabled) return lfa_fail(s, LFA_E_HIP, "a device-side wait of the pressure solve was given up twice");
-		s->stat_co_reason = (uint64_t)(unsigned)hstate[18];  // (0x100: a wait ran out | the waiter's XCC id; 0 on a rank that retreats with a peer)
+		s->stat_co_reason = (uint64_t)(unsigned)hstate[LFA_DW_GAVE_UP_REASON];  // (0x100: a wait ran out | the waiter's XCC id; 0 on a rank that retreats with a peer)
 		s->co_disabled = true;
 		++s->stat_co_aborts;
 		s->system_valid = false;
@@ -2001,11 +2001,11 @@ template <typename real> static int solve_t(lfa_sim *s, double dt, double *resid
 	const int iters = done >= 0 ? done : maxit;
 	double res = 0.0;
 	if (done > 0) {
-		memcpy(&res, hstate + 16, 8);  // (left beside the state words by the kernel that ended the solve)
+		memcpy(&res, hstate + LFA_DW_RESIDUAL, 8);  // (left beside the state words by the kernel that ended the solve)
 	} else if (iters > 0) {
-		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + 4, s->pcg_hist + (iters - 1), 8, hipMemcpyDeviceToHost, s->stream));
+		LFA_HIP(s, hipMemcpyAsync(s->h_pinned + LFA_PIN_LAST_RESIDUAL, s->pcg_hist + (iters - 1), 8, hipMemcpyDeviceToHost, s->stream));
 		LFA_HIP(s, hipStreamSynchronize(s->stream));
-		memcpy(&res, s->h_pinned + 4, 8);
+		memcpy(&res, s->h_pinned + LFA_PIN_LAST_RESIDUAL, 8);
 	}
 	s->last_residual = res;
 	s->last_iters = (uint64_t)iters;
@@ -2095,8 +2095,8 @@ extern "C" int lfa_upload_pressure(lfa_sim *s, const double *p, uint64_t n) {
 
 template <typename real> static int apply_precon_t(lfa_sim *s, const double *r, double *z, uint64_t n) {
 	LFA_TRY(scatter<real>(s, (real *)s->vr, r, n));
-	int init_state[4] = {-1, 0, 0, 0};
-	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, 16, hipMemcpyHostToDevice, s->stream));
+	int init_state[LFA_DW_SOLVER_WORDS] = {-1, 0, 0, 0};
+	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, sizeof init_state, hipMemcpyHostToDevice, s->stream));
 	if (s->n_ptiles) {
 		LFA_TRY(mic_apply<real>(s, s->partials + PART_SIG0));
 		// (the closed tiles are no part of the V-cycle: their share of M^-1 is their exact inverse)
@@ -2117,8 +2117,8 @@ extern "C" int lfa_apply_preconditioner(lfa_sim *s, const double *r, double *z, 
 }
 template <typename real> static int apply_a_t(lfa_sim *s, const double *vin, double *out, uint64_t n) {
 	LFA_TRY(scatter<real>(s, (real *)s->vs, vin, n));
-	int init_state[4] = {-1, 0, 0, 0};
-	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, 16, hipMemcpyHostToDevice, s->stream));
+	int init_state[LFA_DW_SOLVER_WORDS] = {-1, 0, 0, 0};
+	LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, sizeof init_state, hipMemcpyHostToDevice, s->stream));
 	if (s->dist) LFA_TRY(lfa_dist_exchange_slices(s, s->vs, (int)sizeof(real)));
 	if (s->n_ptiles) {
 		TileCtx tc = make_ctx(s);
@@ -2135,53 +2135,51 @@ extern "C" int lfa_apply_a(lfa_sim *s, const double *v, double *out, uint64_t n)
 }
 
 // ================================================================================================= whole hot path
-static int ev_rec(lfa_sim *s, int i) {
-	if (s->timing) LFA_HIP(s, hipEventRecord(s->ev[i], s->stream));
-	return LFA_OK;
-}
-
 extern "C" int lfa_step_hot(lfa_sim *s, double dt, double *residual, uint64_t *iterations) {
 	if (!s) return LFA_E_INVALID;
 	LFA_HIP(s, hipSetDevice(s->device));
 	LFA_TRY(lfa_corr_commit(s));
-	LFA_TRY(ev_rec(s, 0));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_START));
 	LFA_TRY(lfa_hash_particles(s));
-	LFA_TRY(ev_rec(s, 1));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_BIN));
 	LFA_TRY(lfa_p2g_run(s, true, dt));  // gravity fused into the normalise pass
-	LFA_TRY(ev_rec(s, 2));
-	LFA_TRY(ev_rec(s, 3));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_P2G));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_GRAVITY));
 	LFA_TRY(lfa_pcg_alloc(s));
-	LFA_TRY(ev_rec(s, 4));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_ALLOC));
 	double res = 0.0;
 	uint64_t it = 0;
 	int rc = lfa_pcg_solve(s, dt, &res, &it);
 	if (rc < 0) return rc;
-	LFA_TRY(ev_rec(s, 5));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_SOLVE));
 	LFA_TRY(lfa_apply_pressure(s, dt));
-	LFA_TRY(ev_rec(s, 6));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_APPLY));
 	LFA_TRY(lfa_extrapolate(s));
-	LFA_TRY(ev_rec(s, 7));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_EXTRAP));
 	LFA_TRY(lfa_g2p(s));
-	LFA_TRY(ev_rec(s, 8));
+	LFA_TRY(lfa_ev_record(s, LFA_EV_HOT_G2P));
 	if (residual) *residual = res;
 	if (iterations) *iterations = it;
 	if (s->timing) {
-		LFA_HIP(s, hipEventSynchronize(s->ev[8]));
-		float ms = 0.f;
-		const int pairs[8][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}};
-		for (int k = 0; k < 8; ++k) {
-			LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[pairs[k][0]], s->ev[pairs[k][1]]));
-			s->ms[k] = ms;
+		LFA_HIP(s, hipEventSynchronize(s->ev[LFA_EV_HOT_G2P]));
+		static const lfa_span spans[] = {
+			{LFA_TIMER_BIN, LFA_EV_HOT_START, LFA_EV_HOT_BIN},
+			{LFA_TIMER_P2G, LFA_EV_HOT_BIN, LFA_EV_HOT_P2G},
+			{LFA_TIMER_GRAVITY, LFA_EV_HOT_P2G, LFA_EV_HOT_GRAVITY},
+			{LFA_TIMER_BUILD_SYSTEM, LFA_EV_HOT_GRAVITY, LFA_EV_HOT_ALLOC},
+			{LFA_TIMER_PCG_LOOP, LFA_EV_HOT_ALLOC, LFA_EV_HOT_SOLVE},
+			{LFA_TIMER_APPLY_PRESSURE, LFA_EV_HOT_SOLVE, LFA_EV_HOT_APPLY},
+			{LFA_TIMER_EXTRAPOLATE, LFA_EV_HOT_APPLY, LFA_EV_HOT_EXTRAP},
+			{LFA_TIMER_G2P, LFA_EV_HOT_EXTRAP, LFA_EV_HOT_G2P},
+			{LFA_TIMER_P2G_SCATTER_KERNEL, LFA_EV_SCATTER_BEGIN, LFA_EV_SCATTER_END},
+		};
+		LFA_TRY(lfa_fill_spans(s, spans, s->ms));
+		if (it || s->n_ptiles) {  // a solve ran: the split is at the end of the system build, recorded inside it
+			static const lfa_span split[] = {{LFA_TIMER_BUILD_SYSTEM, LFA_EV_HOT_ALLOC, LFA_EV_SYSTEM_BUILT},
+			                                 {LFA_TIMER_PCG_LOOP, LFA_EV_SYSTEM_BUILT, LFA_EV_HOT_SOLVE}};
+			LFA_TRY(lfa_fill_spans(s, split, s->ms));
 		}
-		LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[16], s->ev[17]));
-		s->ms[8] = ms;
-		if (it || s->n_ptiles) {  // split [3]/[4] at the end of the system build recorded inside the solve
-			LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[4], s->ev[18]));
-			s->ms[3] = ms;
-			LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[18], s->ev[5]));
-			s->ms[4] = ms;
-		}
-		s->ms[9] = it ? s->ms[4] / (double)it : 0.0;
+		s->ms[LFA_TIMER_PCG_ITERATION_MEAN] = it ? s->ms[LFA_TIMER_PCG_LOOP] / (double)it : 0.0;
 	}
 	return rc;
 }
@@ -2224,7 +2222,7 @@ template <typename real> static int bench_launch(lfa_sim *s, int which) {
 		launch_pcg_a<real>(false, is_ml(s), is_mg(s) ? G : GA, s->stream, n_it, (const int *)s->nbr_table, (const uint8_t *)s->abits,
 		                   (const real *)v.z, (const real *)v.s, (real *)s->vs2, v.q, scale, (const double *)(P + PART_SIG0), G,
 		                   (const double *)(P + PART_SIG0), G, (const double *)(P + PART_RMAX), G, -HUGE_VAL, 1, s->pcg_state,
-		                   s->pcg_hist + 4095, P + PART_ZS, is_ml(s) ? (const real *)s->c_x : (const real *)nullptr,
+		                   s->pcg_hist + LFA_HIST_BENCH_SINK, P + PART_ZS, is_ml(s) ? (const real *)s->c_x : (const real *)nullptr,
 		                   (const real *)s->c_x2, is_ml(s) ? (real *)s->c_as : (real *)nullptr);
 		break;
 	case LFA_K_PCG_B: {
@@ -2262,8 +2260,8 @@ extern "C" int lfa_bench_kernel(lfa_sim *s, int which, int reps, double *mean_ms
 	                    which == LFA_K_PCG_A || which == LFA_K_PCG_B || (which >= LFA_K_MG_AXPY_PRESMOOTH && which <= LFA_K_MG_UP0);
 	if (is_pcg) {
 		if (!s->system_valid) return lfa_fail(s, LFA_E_INVALID, "lfa_bench_kernel: no pressure system on the device");
-		int init_state[4] = {-1, 0, 0, 0};  // "still iterating": the kernels early-out once a solve has converged
-		LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, 16, hipMemcpyHostToDevice, s->stream));
+		int init_state[LFA_DW_SOLVER_WORDS] = {-1, 0, 0, 0};  // "still iterating": the kernels early-out once a solve has converged
+		LFA_HIP(s, hipMemcpyAsync(s->pcg_state, init_state, sizeof init_state, hipMemcpyHostToDevice, s->stream));
 	}
 	auto once = [&]() -> int {
 		if (is_pcg) return F64(s) ? bench_launch<double>(s, which) : bench_launch<float>(s, which);
@@ -2277,20 +2275,20 @@ extern "C" int lfa_bench_kernel(lfa_sim *s, int which, int reps, double *mean_ms
 		// between the timed calls, outside the timed intervals
 		for (int i = 0; i < reps; ++i) {
 			LFA_TRY(lfa_particles_materialize(s));
-			LFA_HIP(s, hipEventRecord(s->ev[20], s->stream));
+			LFA_HIP(s, hipEventRecord(s->ev[LFA_EV_BENCH_BEGIN], s->stream));
 			LFA_TRY(once());
-			LFA_HIP(s, hipEventRecord(s->ev[21], s->stream));
-			LFA_HIP(s, hipEventSynchronize(s->ev[21]));
+			LFA_HIP(s, hipEventRecord(s->ev[LFA_EV_BENCH_END], s->stream));
+			LFA_HIP(s, hipEventSynchronize(s->ev[LFA_EV_BENCH_END]));
 			float one = 0.f;
-			LFA_HIP(s, hipEventElapsedTime(&one, s->ev[20], s->ev[21]));
+			LFA_HIP(s, hipEventElapsedTime(&one, s->ev[LFA_EV_BENCH_BEGIN], s->ev[LFA_EV_BENCH_END]));
 			ms += one;
 		}
 	} else {
-		LFA_HIP(s, hipEventRecord(s->ev[20], s->stream));
+		LFA_HIP(s, hipEventRecord(s->ev[LFA_EV_BENCH_BEGIN], s->stream));
 		for (int i = 0; i < reps; ++i) LFA_TRY(once());
-		LFA_HIP(s, hipEventRecord(s->ev[21], s->stream));
-		LFA_HIP(s, hipEventSynchronize(s->ev[21]));
-		LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[20], s->ev[21]));
+		LFA_HIP(s, hipEventRecord(s->ev[LFA_EV_BENCH_END], s->stream));
+		LFA_HIP(s, hipEventSynchronize(s->ev[LFA_EV_BENCH_END]));
+		LFA_HIP(s, hipEventElapsedTime(&ms, s->ev[LFA_EV_BENCH_BEGIN], s->ev[LFA_EV_BENCH_END]));
 	}
 	*mean_ms = (double)ms / reps;
 	s->system_valid = is_pcg ? s->system_valid : false;

@@ -60,3 +60,38 @@ def test_seed_block_is_deterministic_and_in_cell():
     # 2x2x2 sub-cell stratification: one particle per octant
     octant = ((a["pos"] - cell) >= 0.5).astype(int) @ np.array([1, 2, 4])
     assert np.array_equal(np.sort(octant.reshape(-1, 8), axis=1), np.tile(np.arange(8), (27, 1)))
+
+
+def header_enum(prefix):
+    """Names (prefix stripped, lower case) and values of the enum of include/libfluid_amd.h whose enumerators start with `prefix`."""
+    text = open(os.path.join(ROOT, "include", "libfluid_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    bodies = [b for b in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S) if re.search(r"\b" + prefix + r"[A-Z0-9_]+", b)]
+    assert len(bodies) == 1, (prefix, len(bodies))
+    names, values, nxt = [], [], 0
+    for item in (i.strip() for i in bodies[0].split(",")):
+        if not item:
+            continue
+        m = re.fullmatch(r"([A-Z0-9_]+)(?:\s*=\s*(-?\d+))?", item)
+        assert m and m.group(1).startswith(prefix), item
+        nxt = int(m.group(2)) if m.group(2) else nxt
+        names.append(m.group(1)[len(prefix):].lower())
+        values.append(nxt)
+        nxt += 1
+    return names, values
+
+
+def header_define(name):
+    text = open(os.path.join(ROOT, "include", "libfluid_amd.h")).read()
+    return int(re.search(r"^#define\s+" + name + r"\s+(\d+)\s*$", text, flags=re.M).group(1))
+
+
+@pytest.mark.parametrize("prefix,count,names", [("LFA_TIMER_", "LFA_NUM_TIMERS", lfa.TIMER_NAMES),
+                                                ("LFA_STEP_TIMER_", "LFA_NUM_STEP_TIMERS", lfa.STEP_TIMER_NAMES)])
+def test_timer_enums_are_the_binding_s_name_lists(prefix, count, names):
+    """The drivers fill their timer arrays by these enumerators; the binding (and bench.py through it) reads them by position."""
+    got, values = header_enum(prefix)
+    assert got == names
+    assert values == list(range(len(names)))
+    assert header_define(count) == len(names)
+    assert (lfa.NUM_TIMERS, lfa.NUM_STEP_TIMERS) == (len(lfa.TIMER_NAMES), len(lfa.STEP_TIMER_NAMES))
