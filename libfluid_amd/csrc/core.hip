@@ -1025,6 +1025,7 @@ __global__ void k_gather_vc(size_t n, ParticleSoA old, ParticleSoA cur, const ui
 
 /// Particles per cell for every processed tile (the `count` half of _space_hash, src/simulation.cpp:266-291);
 /// tiles of the dilated set that hold no particles get zeros.
+#define CC_UNROLL 16
 __global__ void __launch_bounds__(256)
 k_cell_count(const int *dtiles, int n_dtiles, const uint32_t *key, const uint32_t *tile_start, uint32_t *cell_count) {
 	__shared__ uint32_t cnt[LFA_TILE_CELLS];
@@ -1034,7 +1035,19 @@ k_cell_count(const int *dtiles, int n_dtiles, const uint32_t *key, const uint32_
 		cnt[threadIdx.x + 256] = 0;
 		__syncthreads();
 		uint32_t b = tile_start[tile], e = tile_start[tile + 1];
-		for (uint32_t i = b + threadIdx.x; i < e; i += 256) atomicAdd(&cnt[key[i] & 511], 1u);
+		// CC_UNROLL key loads per thread - a whole tile of 4 096 - are issued before the first LDS atomic (one load per round
+		// into an atomic is one memory round trip per round); past the end the load is clamped and its key not counted
+		for (uint32_t base = b + threadIdx.x; base - threadIdx.x < e; base += 256 * CC_UNROLL) {
+			uint32_t k[CC_UNROLL];
+#pragma unroll
+			for (int q = 0; q < CC_UNROLL; ++q) {
+				const uint32_t i = base + 256 * q;
+				k[q] = key[i < e ? i : e - 1];
+			}
+#pragma unroll
+			for (int q = 0; q < CC_UNROLL; ++q)
+				if (base + 256 * q < e) atomicAdd(&cnt[k[q] & 511], 1u);
+		}
 		__syncthreads();
 		cell_count[(size_t)tile * LFA_TILE_CELLS + threadIdx.x] = cnt[threadIdx.x];
 		cell_count[(size_t)tile * LFA_TILE_CELLS + 256 + threadIdx.x] = cnt[threadIdx.x + 256];

@@ -293,12 +293,12 @@ struct G2PParams {
 /// sample of field (0-2: u v w, 3-5: FLIP's old grid) at that cell + ((k & 1), (k >> 1) & 1, k >> 2).
 /// `pold`, `j`: where FLIP finds the particle's velocity from before the step (a deferred binning leaves it in the other buffer).
 /// Returns |v|^2 of the new velocity (the CFL reduction of simulation::cfl rides along, src/simulation.cpp:199-205).
+/// g2p_particle = its loads (the fractions `t`, FLIP's old velocity `vp`), g2p_transfer - registers in, registers out (the new
+/// velocity `vout`, APIC's `cvec`) - and g2p_store: k_g2p runs the three apart, with the next particle's loads in between.
 template <int METHOD, typename Corner, typename Fetch>
-__device__ inline float g2p_particle(const ParticleSoA &p, uint32_t i, const ParticleSoA &pold, uint32_t j, const G2PParams &gp,
-                                    Corner &&corner, Fetch &&fetch) {
-	const float t[3] = {p.t[0][i], p.t[1][i], p.t[2][i]};
+__device__ inline float g2p_transfer(const float (&t)[3], const float (&vp)[3], const G2PParams &gp, Corner &&corner, Fetch &&fetch,
+                                    float (&vout)[3], float (&cvec)[9]) {
 	float vnew[3], vold[3];
-	float cvec[9];
 #pragma unroll
 	for (int comp = 0; comp < 3; ++comp) {
 		// (b, f) per axis exactly as in the P2G scatter: own axis -> (idx-1, t), other axes -> (d-1, tmid)
@@ -343,21 +343,45 @@ __device__ inline float g2p_particle(const ParticleSoA &p, uint32_t i, const Par
 			cvec[3 * comp] = cx; cvec[3 * comp + 1] = cy; cvec[3 * comp + 2] = cz;
 		}
 	}
-	float vout[3];
 	if (METHOD == LFA_FLIP_BLEND) {
 #pragma unroll
-		for (int k = 0; k < 3; ++k) vout[k] = vnew[k] + (pold.v[k][j] - vold[k]) * gp.blend;
+		for (int k = 0; k < 3; ++k) vout[k] = vnew[k] + (vp[k] - vold[k]) * gp.blend;
 	} else {
 #pragma unroll
 		for (int k = 0; k < 3; ++k) vout[k] = vnew[k];
 	}
+	return vout[0] * vout[0] + vout[1] * vout[1] + vout[2] * vout[2];
+}
+template <int METHOD>
+__device__ inline void g2p_store(const ParticleSoA &p, uint32_t i, const float (&vout)[3], const float (&cvec)[9]) {
 #pragma unroll
 	for (int k = 0; k < 3; ++k) p.v[k][i] = vout[k];
 	if (METHOD == LFA_APIC) {
 #pragma unroll
 		for (int k = 0; k < 9; ++k) p.c[k][i] = cvec[k];
 	}
-	return vout[0] * vout[0] + vout[1] * vout[1] + vout[2] * vout[2];
+}
+template <int METHOD, typename Corner, typename Fetch>
+__device__ inline float g2p_particle(const ParticleSoA &p, uint32_t i, const ParticleSoA &pold, uint32_t j, const G2PParams &gp,
+                                    Corner &&corner, Fetch &&fetch) {
+	const float t[3] = {p.t[0][i], p.t[1][i], p.t[2][i]};
+	float vp[3] = {0.0f, 0.0f, 0.0f}, vout[3], cvec[9];
+	if (METHOD == LFA_FLIP_BLEND) {
+#pragma unroll
+		for (int k = 0; k < 3; ++k) vp[k] = pold.v[k][j];
+	}
+	const float v2 = g2p_transfer<METHOD>(t, vp, gp, corner, fetch, vout, cvec);
+	g2p_store<METHOD>(p, i, vout, cvec);
+	return v2;
+}
+
+/// Takes delivery of loaded values: the compiler's wait for the loads that produce a .. d stands here, not at their first use
+/// further down. For loads issued ahead of stores: loads and stores share one counter (vmcnt), and hipcc waits for a load with
+/// vmcnt(0) whenever a store is pending beside it - a use behind the stores waits for the stores' acknowledgement as well. Emits
+/// no instruction of its own; memory accesses are not moved across it.
+template <typename A, typename B, typename C, typename D>
+__device__ inline void lfa_take_delivery(A &a, B &b, C &c, D &d) {
+	asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : : "memory");
 }
 
 /// One workgroup per particle tile: stage u,v,w (and FLIP's old grid) of the tile + 1-cell ring in LDS with the
@@ -382,37 +406,103 @@ k_g2p(const int *ptiles, int n_ptiles, GridDims g, ParticleSoA p, const uint32_t
 		const int tile = ptiles[slot];
 		int tx, ty, tz;
 		tile_coords(g, tile, tx, ty, tz);
+		// staging: every load of the thread's halo cells is issued before the first LDS write. The cell read is the clamped one
+		// whether or not the sample is the zero of a clamped axis (clamped_sample branches around its load, and a branch per
+		// load is a round trip per load).
+		constexpr int HR = (LFA_HALO_CELLS + G2P_THREADS - 1) / G2P_THREADS;
+		const float *F[6] = {u, v, w, uo, vo, wo};
+		const int nn[3] = {g.nx, g.ny, g.nz};
+		float hv[HR][NF];
+		uint32_t hb[HR];
+#pragma unroll
+		for (int r = 0; r < HR; ++r) {
+			const int i = min((int)threadIdx.x + G2P_THREADS * r, LFA_HALO_CELLS - 1);
+			const int x = tx * 8 + i % 10 - 1, y = ty * 8 + (i / 10) % 10 - 1, z = tz * 8 + i / 100 - 1;
+			hb[r] = blocked_index(g, min(max(x, 0), g.nx - 1), min(max(y, 0), g.ny - 1), min(max(z, 0), g.nz - 1));
+		}
+#pragma unroll
+		for (int r = 0; r < HR; ++r) {
+#pragma unroll
+			for (int f = 0; f < NF; ++f) hv[r][f] = F[f][hb[r]];
+		}
 		__syncthreads();
 		if (STALE && threadIdx.x == 0) lv_n = 0;
-		for (int i = threadIdx.x; i < LFA_HALO_CELLS; i += G2P_THREADS) {
-			const int hx = i % 10, hy = (i / 10) % 10, hz = i / 100;
-			const int x = tx * 8 + hx - 1, y = ty * 8 + hy - 1, z = tz * 8 + hz - 1;
-			lds[i] = clamped_sample(g, u, 0, x, y, z);
-			lds[LFA_HALO_CELLS + i] = clamped_sample(g, v, 1, x, y, z);
-			lds[2 * LFA_HALO_CELLS + i] = clamped_sample(g, w, 2, x, y, z);
-			if (METHOD == LFA_FLIP_BLEND) {
-				lds[3 * LFA_HALO_CELLS + i] = clamped_sample(g, uo, 0, x, y, z);
-				lds[4 * LFA_HALO_CELLS + i] = clamped_sample(g, vo, 1, x, y, z);
-				lds[5 * LFA_HALO_CELLS + i] = clamped_sample(g, wo, 2, x, y, z);
+#pragma unroll
+		for (int r = 0; r < HR; ++r) {
+			const int i = (int)threadIdx.x + G2P_THREADS * r;
+			if (i < LFA_HALO_CELLS) {
+				const int c[3] = {tx * 8 + i % 10 - 1, ty * 8 + (i / 10) % 10 - 1, tz * 8 + i / 100 - 1};
+#pragma unroll
+				for (int f = 0; f < NF; ++f) {
+					const int comp = f % 3;
+					lds[f * LFA_HALO_CELLS + i] = (c[comp] < 0 || c[comp] >= nn[comp] - 1) ? 0.0f : hv[r][f];
+				}
 			}
 		}
 		__syncthreads();
 		const uint32_t beg = tile_start[tile], end = tile_start[tile + 1];
-		for (uint32_t i = beg + threadIdx.x; i < end; i += G2P_THREADS) {
-			const uint32_t key = p.key[i];
-			if (STALE && (int)(key >> 9) != tile) {
-				const uint32_t at = atomicAdd(&lv_n, 1u);
-				if (at < G2P_LV_CAP) lv[at] = i;
-				else leavers[atomicAdd(n_leavers, 1u)] = i;  // more than the LDS list holds: straight to the global list
-				continue;
+		// software pipeline, as in k_p2g_binned: the loads of the thread's next particle - key, fractions, and for FLIP the
+		// velocity from before the step - are in flight while the current one gathers from LDS and stores; with a deferred
+		// binning (`from`) the index of the particle after next is loaded one round ahead of the velocity it names. The loads are
+		// unconditional: past the end of the tile they read the tile's last slot and the result is dropped.
+		// FLIP on a handle without a deferred binning reads and writes the same velocity arrays (pold == p, j == i): a
+		// prefetched slot is always this thread's own LATER slot, i + G2P_THREADS, which nobody has written yet - a thread
+		// writes slot i only after it has read it, and no other thread touches it. (The read past the end, which is dropped, may
+		// be of another thread's slot, written or not.)
+		constexpr bool FLIP = METHOD == LFA_FLIP_BLEND;
+		struct Regs {
+			uint32_t key;
+			float t[3], vp[3];
+		} cur, nxt;
+		auto load = [&](uint32_t i, uint32_t j, Regs &r) {
+			r.key = p.key[i];
+#pragma unroll
+			for (int k = 0; k < 3; ++k) {
+				r.t[k] = p.t[k][i];
+				r.vp[k] = FLIP ? pold.v[k][j] : 0.0f;
 			}
-			const int l = (int)(key & 511);
-			const int cell = ((l & 7) + 1) + 10 * (((l >> 3) & 7) + 1) + 100 * ((l >> 6) + 1);
-			const float v2 = g2p_particle<METHOD>(
-			    p, i, pold, (METHOD == LFA_FLIP_BLEND && from) ? from[i] : i, gp,
-			    [&](int b0, int b1, int b2) { return cell + b0 + 10 * b1 + 100 * b2; },
-			    [&](int field, int, int base, int k) { return lds[field * LFA_HALO_CELLS + base + (k & 1) + 10 * ((k >> 1) & 1) + 100 * (k >> 2)]; });
-			vmax2 = fmaxf(vmax2, v2);
+		};
+		if (beg < end) {
+			const uint32_t last = end - 1;
+			uint32_t i = beg + threadIdx.x;
+			uint32_t jn = 0;
+			if (FLIP) jn = from ? from[min(i + G2P_THREADS, last)] : min(i + G2P_THREADS, last);
+			load(min(i, last), FLIP ? (from ? from[min(i, last)] : min(i, last)) : 0u, cur);
+			// (the first round needs them at once anyway; with loads pending on entry the compiler's wait at the top of the loop
+			// would cover the back edge too, where only the last round's stores are pending)
+			lfa_take_delivery(cur.key, cur.t[0], cur.t[1], cur.t[2]);
+			if (FLIP) lfa_take_delivery(jn, cur.vp[0], cur.vp[1], cur.vp[2]);
+			for (; i < end; i += G2P_THREADS) {
+				const uint32_t in = min(i + G2P_THREADS, last);
+				uint32_t jnn = 0;
+				if (FLIP) jnn = from ? from[min(i + 2 * G2P_THREADS, last)] : min(i + 2 * G2P_THREADS, last);
+				load(in, jn, nxt);
+				jn = jnn;
+				const uint32_t key = cur.key;
+				const bool leaver = STALE && (int)(key >> 9) != tile;
+				float vout[3], cvec[9];
+				if (leaver) {
+					const uint32_t at = atomicAdd(&lv_n, 1u);
+					if (at < G2P_LV_CAP) lv[at] = i;
+					else leavers[atomicAdd(n_leavers, 1u)] = i;  // more than the LDS list holds: straight to the global list
+				} else {
+					const int l = (int)(key & 511);
+					const int cell = ((l & 7) + 1) + 10 * (((l >> 3) & 7) + 1) + 100 * ((l >> 6) + 1);
+					const float v2 = g2p_transfer<METHOD>(
+					    cur.t, cur.vp, gp, [&](int b0, int b1, int b2) { return cell + b0 + 10 * b1 + 100 * b2; },
+					    [&](int field, int, int base, int k) { return lds[field * LFA_HALO_CELLS + base + (k & 1) + 10 * ((k >> 1) & 1) + 100 * (k >> 2)]; },
+					    vout, cvec);
+					vmax2 = fmaxf(vmax2, v2);
+				}
+				// The next particle's loads are taken delivery of HERE, after the gather and before this round's stores: the compiler
+				// waits for a load with vmcnt(0) whenever a store is pending with it (loads and stores share the counter), so a wait
+				// placed after the stores would wait for their acknowledgement too. This way the stores of round r are followed at
+				// once by the loads of round r + 2.
+				cur = nxt;
+				lfa_take_delivery(cur.key, cur.t[0], cur.t[1], cur.t[2]);
+				if (FLIP) lfa_take_delivery(jn, cur.vp[0], cur.vp[1], cur.vp[2]);
+				if (!leaver) g2p_store<METHOD>(p, i, vout, cvec);
+			}
 		}
 		if (STALE) {  // one global atomic per tile
 			__syncthreads();

@@ -171,41 +171,54 @@ __global__ void k_tile_clear(GridDims g, const uint8_t *tile_solid, uint8_t *til
 	tile_clear[t] = (uint8_t)(any ? 0 : 1);
 }
 
+/// One particle of the advection between its loads and its stores. The kernels run three phases - load, move, store - over all
+/// of a thread's particles, so that every load is in flight before the first is consumed and none is issued behind a store:
+/// stores count in vmcnt on this hardware, and a wait for a load issued after them waits for their acknowledgement too.
+struct AdvectSlot {
+	uint32_t key;    // in: the old key (0xFFFFFFFF: no particle); out: the new one
+	float t[3];      // in: the old fractions; out: the new ones
+	float v[3];      // in: the velocity; out (a coerced particle): the source's
+	uint32_t clear;  // tile_clear of the old tile
+	uint32_t src;    // COERCE: 1 + the coercing source of the old cell, 0 = none
+};
+/// Load phase, first round trip: what does not depend on the key. Unconditional: the caller clamps an index >= n to a valid one
+/// and marks the slot invalid afterwards; the values of an invalid slot are never used.
+__device__ inline void advect_load(size_t i, const ParticleSoA &p, AdvectSlot &a) {
+	a.key = p.key[i];
+#pragma unroll
+	for (int d = 0; d < 3; ++d) {
+		a.t[d] = p.t[d][i];
+		a.v[d] = p.v[d][i];
+	}
+}
+/// Load phase, second round trip: the bytes the key names (an invalid key reads entry 0 and ignores it).
+template <bool COERCE>
+__device__ inline void advect_load_by_key(const uint8_t *coerce_map, const uint8_t *tile_clear, AdvectSlot &a) {
+	const uint32_t k = a.key != 0xFFFFFFFFu ? a.key : 0u;
+	a.clear = tile_clear[k >> 9];
+	a.src = COERCE ? (uint32_t)coerce_map[k] : 0u;
+}
+/// Move phase: registers in, registers out; the only memory it touches is the solid mask of the general collide() march (and
+/// the source's velocity of a coerced particle), read-only. Returns the new key (0xFFFFFFFF for an invalid slot).
 /// COERCE: the velocity coercion of the fluid sources first (src/simulation.cpp:227-238): a particle inside a cell of an active
 /// coercing source takes the source's velocity and C = 0 (the cell is the particle's current one: the reference hashes at the
 /// start of the step, :49).
 template <bool COERCE>
-__device__ inline uint32_t advect_one(size_t i, const ParticleSoA &p, const GridDims &g, const uint8_t *solid, const MoveParams &mp,
-                                      const uint8_t *coerce_map, const float *src_vel, const uint8_t *tile_clear) {
-	const uint32_t key = p.key[i];
+__device__ inline uint32_t advect_move(AdvectSlot &a, const GridDims &g, const uint8_t *solid, const MoveParams &mp, const float *src_vel) {
+	const uint32_t key = a.key;
 	if (key == 0xFFFFFFFFu) return key;  // outside this rank's slab (dropped at the next binning)
 	int c[3];
 	cell_of_key(g, key, c);
 	const int nn[3] = {g.nx, g.ny, g.nz};
-	float vel[3] = {p.v[0][i], p.v[1][i], p.v[2][i]};
-	if (COERCE) {
-		const uint32_t src = coerce_map[key];
-		if (src) {
+	if (COERCE && a.src) {
 #pragma unroll
-			for (int d = 0; d < 3; ++d) {
-				vel[d] = src_vel[3 * (src - 1) + d];
-				p.v[d][i] = vel[d];
-			}
-			if (mp.c_home) {
-				const size_t j = p.id[i];
-#pragma unroll
-				for (int k = 0; k < 9; ++k) mp.c_home[k * mp.c_home_stride + j] = 0.0f;
-			} else {
-#pragma unroll
-				for (int k = 0; k < 9; ++k) p.c[k][i] = 0.0f;
-			}
-		}
+		for (int d = 0; d < 3; ++d) a.v[d] = src_vel[3 * (a.src - 1) + d];
 	}
 	double from[3], to[3];
 #pragma unroll
 	for (int d = 0; d < 3; ++d) {
-		from[d] = (double)c[d] + (double)p.t[d][i];
-		double x = from[d] + (double)vel[d] * mp.dt_over_h;
+		from[d] = (double)c[d] + (double)a.t[d];
+		double x = from[d] + (double)a.v[d] * mp.dt_over_h;
 		const double lo = mp.skin, hi = (double)nn[d] - mp.skin;
 		to[d] = x < lo ? lo : (hi < x ? hi : x);
 	}
@@ -216,19 +229,36 @@ __device__ inline uint32_t advect_one(size_t i, const ParticleSoA &p, const Grid
 	// farthest, but possibly in its far cell layer (7.95 -> 15.93), whose neighbour (cell 16) lies two tiles from the start, where
 	// tile_clear says nothing; below 7 cells the end cell is at most 7 + 7 = 14 (or 8 - 7 = 1) and its neighbours are covered.
 	// The general path costs a dependent byte load per crossed cell and per near face; most tiles of a scene are nowhere near a
-	// solid.
-	const bool open_water = (tile_clear[key >> 9] & 1) && fabs(to[0] - from[0]) < 7.0 && fabs(to[1] - from[1]) < 7.0 &&
+	// solid. Those loads wait for nothing but themselves: no store of any slot has been issued yet.
+	const bool open_water = (a.clear & 1) && fabs(to[0] - from[0]) < 7.0 && fabs(to[1] - from[1]) < 7.0 &&
 	                        fabs(to[2] - from[2]) < 7.0;
 	if (!open_water && mp.collide) collide(g, solid, from, to, mp.skin);
 	int nc[3];
-	float nt[3];
 #pragma unroll
-	for (int d = 0; d < 3; ++d) split_position(to[d], nn[d], nc[d], nt[d]);
-	const uint32_t new_key = blocked_index(g, nc[0], nc[1], nc[2]);
-	p.key[i] = new_key;
+	for (int d = 0; d < 3; ++d) split_position(to[d], nn[d], nc[d], a.t[d]);
+	a.key = blocked_index(g, nc[0], nc[1], nc[2]);
+	return a.key;
+}
+/// Store phase: key and fractions of a valid slot; of a coerced one the source's velocity and C = 0 as well (rare: its id load
+/// is the one load that follows a store).
+template <bool COERCE>
+__device__ inline void advect_store(size_t i, const ParticleSoA &p, const MoveParams &mp, const AdvectSlot &a) {
+	if (a.key == 0xFFFFFFFFu) return;
+	p.key[i] = a.key;
 #pragma unroll
-	for (int d = 0; d < 3; ++d) p.t[d][i] = nt[d];
-	return new_key;
+	for (int d = 0; d < 3; ++d) p.t[d][i] = a.t[d];
+	if (COERCE && a.src) {
+#pragma unroll
+		for (int d = 0; d < 3; ++d) p.v[d][i] = a.v[d];
+		if (mp.c_home) {
+			const size_t j = p.id[i];
+#pragma unroll
+			for (int k = 0; k < 9; ++k) mp.c_home[k * mp.c_home_stride + j] = 0.0f;
+		} else {
+#pragma unroll
+			for (int k = 0; k < 9; ++k) p.c[k][i] = 0.0f;
+		}
+	}
 }
 
 template <bool COERCE>
@@ -236,13 +266,21 @@ __global__ void __launch_bounds__(256)
 k_advect_collide(size_t n, ParticleSoA p, GridDims g, const uint8_t *solid, MoveParams mp, const uint8_t *coerce_map,
                  const float *src_vel, const uint8_t *tile_clear) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) advect_one<COERCE>(i, p, g, solid, mp, coerce_map, src_vel, tile_clear);
+	if (i >= n) return;
+	AdvectSlot a;
+	advect_load(i, p, a);
+	advect_load_by_key<COERCE>(coerce_map, tile_clear, a);
+	advect_move<COERCE>(a, g, solid, mp, src_vel);
+	advect_store<COERCE>(i, p, mp, a);
 }
 
 /// The same with pass 1 of the binning that follows it in lfa_time_step (core.hip: k_tile_count) done on the way: the new keys are
 /// in registers, so a wave ranks its AC_CHUNKS x 64 particles inside their new tiles right here (one atomic per distinct tile) and
 /// the binning neither reads the keys again nor waits for that pass's returning atomics (0.24 ms at C4).
-#define AC_CHUNKS 8  // particles per lane (4: 0.80 ms, 8: 0.74, 16: 0.73 at C4; the plain advection 0.58 + k_tile_count 0.24)
+/// A lane's AC_CHUNKS particles are disjoint indices that no other thread touches, so all of their loads may - and do - come
+/// before the first of their stores: two round trips (the keys, fractions and velocities; then the bytes the keys name), the
+/// moves, the ranking, and the stores (key, fractions, rank) last.
+#define AC_CHUNKS 8  // particles per lane (one after the other: 4: 0.80 ms, 8: 0.74, 16: 0.73 at C4; the plain advection 0.58 + k_tile_count 0.24)
 template <bool COERCE>
 __global__ void __launch_bounds__(256)
 k_advect_collide_count(size_t n, ParticleSoA p, GridDims g, const uint8_t *solid, MoveParams mp, const uint8_t *coerce_map,
@@ -250,17 +288,28 @@ k_advect_collide_count(size_t n, ParticleSoA p, GridDims g, const uint8_t *solid
 	const int lane = threadIdx.x & 63;
 	const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const size_t i0 = wave * (64 * AC_CHUNKS) + lane;
+	AdvectSlot a[AC_CHUNKS];
 	uint32_t tile[AC_CHUNKS], my_rank[AC_CHUNKS];
 #pragma unroll
 	for (int c = 0; c < AC_CHUNKS; ++c) {
 		const size_t i = i0 + 64 * c;
-		const uint32_t k = i < n ? advect_one<COERCE>(i, p, g, solid, mp, coerce_map, src_vel, tile_clear) : 0xFFFFFFFFu;
+		advect_load(i < n ? i : n - 1, p, a[c]);
+	}
+#pragma unroll
+	for (int c = 0; c < AC_CHUNKS; ++c) {
+		if (i0 + 64 * c >= n) a[c].key = 0xFFFFFFFFu;
+		advect_load_by_key<COERCE>(coerce_map, tile_clear, a[c]);
+	}
+#pragma unroll
+	for (int c = 0; c < AC_CHUNKS; ++c) {
+		const uint32_t k = advect_move<COERCE>(a[c], g, solid, mp, src_vel);
 		tile[c] = k != 0xFFFFFFFFu ? k >> 9 : 0xFFFFFFFFu;
 	}
 	lfa_wave_tile_ranks(tile, tile_count, my_rank);
 #pragma unroll
 	for (int c = 0; c < AC_CHUNKS; ++c) {
 		const size_t i = i0 + 64 * c;
+		advect_store<COERCE>(i, p, mp, a[c]);
 		if (tile[c] != 0xFFFFFFFFu) rank[i] = my_rank[c];
 	}
 }
@@ -381,17 +430,24 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 		uint32_t rf[RPT];
 		float r0[RPT], r1[RPT], r2[RPT];
 		if (staged) {
+			// all of the thread's loads first, unconditionally (a slot past the end reads the tile's last record and drops it): a
+			// load inside `if (i < e)` is branched around and waited for on its own, RPT round trips where one will do
+			const uint32_t last = e > b ? e - 1 : 0u;
 #pragma unroll
 			for (int r = 0; r < RPT; ++r) {
-				const uint32_t i = b + threadIdx.x + FIDX_THREADS * r;
-				rf[r] = 0xFFFFFFFFu;
-				if (i < e) {
-					int l[3];
-					float t[3];
-					const int f = fine_of(i, l, t);
+				const uint32_t i = min(b + threadIdx.x + FIDX_THREADS * r, last);
+				rf[r] = key[i];
+				r0[r] = t0[i]; r1[r] = t1[i]; r2[r] = t2[i];
+			}
+#pragma unroll
+			for (int r = 0; r < RPT; ++r) {
+				if (b + threadIdx.x + FIDX_THREADS * r < e) {
+					const int l[3] = {(int)(rf[r] & 7), (int)((rf[r] >> 3) & 7), (int)((rf[r] >> 6) & 7)};
+					const int f = fine_coord_x(l[0], r0[r]) + FTX * (fine_coord(l[1], r1[r]) + FT * fine_coord(l[2], r2[r]));
 					rf[r] = ((uint32_t)f << 9) | (uint32_t)(l[0] | (l[1] << 3) | (l[2] << 6));
-					r0[r] = t[0]; r1[r] = t[1]; r2[r] = t[2];
 					atomicAdd(&cnt[f >> 1], 1u << (16 * (f & 1)));
+				} else {
+					rf[r] = 0xFFFFFFFFu;
 				}
 			}
 		} else {
