@@ -139,18 +139,21 @@ def a_scale(name):
 
 
 # ---------------------------------------------------------------------------------------------------- the level-0 system
-def plate_system_of(size):
-    """The A-byte rule (oracle/oracle.c orc_build_system) restated for a plate: every cell of y = 0, 1 holds one particle and is
-    FLUID, every other cell is AIR, outside the grid is solid. tests/test_vcycle_model.py holds it to the oracle's hash + build_system
-    on a small plate."""
+def plate_system_of(size, fluid=None):
+    """The A-byte rule (oracle/oracle.c orc_build_system) restated for a field without solid cells: every cell of `fluid` (bool[nz,
+    ny, nx]; None: the plate, y = 0, 1) holds one particle and is FLUID, every other cell is AIR, outside the grid is solid: ns counts
+    the neighbours inside the grid, bit 3 + d says that the +d neighbour is FLUID. tests/test_vcycle_model.py holds it to the oracle's
+    hash + build_system on a small plate, tests/test_multilevel_model.py on a small plate with holes."""
     nx, ny, nz = size
     z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
-    fluid = y < 2
+    fluid = (y < 2) if fluid is None else np.asarray(fluid, dtype=bool).reshape(nz, ny, nx)
     raw = (x + nx * (y + ny * z))
     fc = np.sort(raw[fluid]).astype(np.uint64)
     cz, cy, cx = fc.astype(np.int64) // (nx * ny), (fc.astype(np.int64) // nx) % ny, fc.astype(np.int64) % nx
     ns = (cx > 0).astype(int) + (cx < nx - 1) + (cy > 0) + (cy < ny - 1) + (cz > 0) + (cz < nz - 1)
-    ab = ns | ((cx < nx - 1) << 3) | ((cy < 1) << 4) | ((cz < nz - 1) << 5)
+    up = [fluid[cz, cy, np.minimum(cx + 1, nx - 1)] & (cx < nx - 1), fluid[cz, np.minimum(cy + 1, ny - 1), cx] & (cy < ny - 1),
+          fluid[np.minimum(cz + 1, nz - 1), cy, cx] & (cz < nz - 1)]
+    ab = ns | (up[0].astype(int) << 3) | (up[1].astype(int) << 4) | (up[2].astype(int) << 5)
     types = np.where(fluid, sc.FLUID, sc.AIR).reshape(-1).astype(np.uint8)
     return dict(size=size, fluid_cells=fc, counts=fluid.reshape(-1).astype(np.uint32), type=types, abits=ab.astype(np.uint8),
                 b=None, p=None, iters=None, vel=np.zeros((nx * ny * nz, 3)))
@@ -336,21 +339,34 @@ def reference(name, label, closed=True, prune=True):
     r = rhs(name)[label]
     z = vm.vcycle(H, r)
     op = vm.open_mask(H)
-    d32 = float(np.abs(vm.vcycle(H, r, dtype=np.float32) - z)[op].max()) if op.any() else 0.0
+    d32 = 0.0
+    if op.any():
+        d32 = fp32_deviation(vm.vcycle(H, r, dtype=np.float32)[op], z[op])
+    z.setflags(write=False)
+    return z, d32
+
+
+F32_BARS = 8.0     # an fp32 result is held to F32_BARS d32
+F64_REL = 1e-10    # an fp64 result to F64_REL max |model|
+
+
+def fp32_deviation(z32, z64):
+    """d32 = max |model_float32 - model_float64|, never below half an fp32 ulp of the largest entry (reference says why). The one
+    place of the rule: tests/multilevel_cases.py takes its bars from here too."""
     # A unit impulse takes a handful of roundings, and the numpy run can be lucky: on `maze`, impulse_last_z, it deviates by 8.5e-9
     # max |z|, a seventh of the HALF ULP of the largest entry, while the device - whose z is stored in fp32 like the model's - is 0.9
     # ulp away (1.19 bars of 8 d32). d32 is therefore never taken below the rounding of the result's storage, 2^-24 max |z| over
     # the V-cycle's unknowns: below that the figure measures luck, not arithmetic. (Recorded in docs/experiments.md.)
-    if op.any():
-        d32 = max(d32, 2.0 ** -24 * float(np.abs(z[op]).max()))
-    z.setflags(write=False)
-    return z, d32
+    z32, z64 = np.asarray(z32, dtype=np.float64), np.asarray(z64, dtype=np.float64)
+    if not z64.size:
+        return 0.0
+    return max(float(np.abs(z32 - z64).max()), 2.0 ** -24 * float(np.abs(z64).max()))
 
 
 def bar(name, label, f64, closed=True, prune=True):
     """The bar of the V-cycle's share of z. fp64: 1e-10 max |z|; fp32: 8 d32."""
     z, d32 = reference(name, label, closed, prune)
-    return 1e-10 * float(np.abs(z).max()) if f64 else 8.0 * d32
+    return F64_REL * float(np.abs(z).max()) if f64 else F32_BARS * d32
 
 
 def closed_bars(H, r, f64, tolerance=1e-6):
