@@ -50,9 +50,17 @@ void lfa_pool_park_set(lfa_stream_set *q);
 #define AB_UNKNOWN 0x40
 #define AB_FLUID 0x80
 
+/// A particle's position: the blocked cell index and the three in-cell fractions, one 16-byte record - every per-step kernel
+/// wants the four together, and 16 bytes per lane is the access this hardware moves fastest (docs/experiments.md, "record width").
+/// The key travels as integer bits (pos_load / pos_store): 0xFFFFFFFF, "no particle", is a NaN pattern.
+struct alignas(16) PosRec {
+	uint32_t key;  // blocked cell index
+	float t[3];    // in-cell fractions, [0, 1]; 1.0f only on the max face
+};
+static_assert(sizeof(PosRec) == 16, "a position record is one 16-byte access");
+
 struct ParticleSoA {
-	uint32_t *key = nullptr;  // blocked cell index
-	float *t[3] = {nullptr, nullptr, nullptr};
+	PosRec *pos = nullptr;
 	float *v[3] = {nullptr, nullptr, nullptr};
 	float *c[9] = {nullptr};  // cx.xyz, cy.xyz, cz.xyz
 	uint32_t *id = nullptr;   // index in the caller's array (upload order)
@@ -102,7 +110,7 @@ struct lfa_sim {
 	bool overlap_correction = true;
 	bool corr_in_flight = false;   // lfa_correct_collide_begin .. _end: the particle arrays belong to the correction on stream3
 	bool counts_fresh = false;     // tile_count / rank were produced by the advection of lfa_time_step: the binning skips its pass 1
-	bool move_pending = false;     // lfa_advect / lfa_correct have moved the particles and lfa_collide is due: the positions of before sit in the other buffer's key / t
+	bool move_pending = false;     // lfa_advect / lfa_correct have moved the particles and lfa_collide is due: the positions of before sit in the other buffer's pos
 	bool corr_begun = false;       // the last lfa_correct_collide_begin started a correction (false: no particles, nothing to take back)
 	bool corr_undo_valid = false;  // nothing has changed positions, binning or solids since: lfa_correct_collide_undo can restore
 	uint32_t *corr_ovf = nullptr;  // tiled correction: word 0 = number of flagged (overflowing) half tiles, then their bitmap
@@ -117,6 +125,8 @@ struct lfa_sim {
 	ParticleSoA pb[2];
 	int cur = 0;
 	uint32_t *rank = nullptr;
+	uint32_t *bkey = nullptr;  // keys alone, in the order of the last binning (pcap words): k_tile_scatter leaves them for the cell
+	                           // count, k_build_fine_index leaves the keys of before the correction (its fallback pass, the undo)
 	bool binned = false;
 
 	// z-slab domain decomposition (dist.hip). Every rank indexes the GLOBAL grid; it owns the tile layers
@@ -453,6 +463,18 @@ __device__ inline void particle_world_position(const GridDims &g, const IngestPa
 	const float t[3] = {t0, t1, t2};
 #pragma unroll
 	for (int k = 0; k < 3; ++k) x[k] = ip.off[k] + ((double)c[k] + (double)t[k]) * ip.h;
+}
+
+/// A position record as one 16-byte load / store.
+__device__ inline PosRec pos_load(const PosRec *pos, size_t i) {
+	const uint4 q = *(const uint4 *)(pos + i);
+	PosRec r;
+	r.key = q.x;
+	r.t[0] = __uint_as_float(q.y); r.t[1] = __uint_as_float(q.z); r.t[2] = __uint_as_float(q.w);
+	return r;
+}
+__device__ inline void pos_store(PosRec *pos, size_t i, uint32_t key, float t0, float t1, float t2) {
+	*(uint4 *)(pos + i) = make_uint4(key, __float_as_uint(t0), __float_as_uint(t1), __float_as_uint(t2));
 }
 
 /// The end of every record a seeding kernel creates: C = 0 and the id.

@@ -356,7 +356,7 @@ extern "C" void lfa_destroy(lfa_sim *s) {
 	lfa_pool_nosync_begin();
 	free_soa(s->pb[0]);
 	free_soa(s->pb[1]);
-	void *ptrs[] = {s->c_home, s->fine_start, s->corr_ovf, s->tile_clear, s->tile_epoch, s->tile_closed, s->src_cell, s->src_lo, s->src_target, s->src_of, s->src_need, s->src_vel, s->src_slab.words, s->coerce_map, s->grid_flag, s->rank, s->vc_src, s->tile_count, s->tile_start, s->tile_flag, s->tile_scan, s->ptiles_all, s->dtiles, s->halo_tiles, s->dist_red,
+	void *ptrs[] = {s->c_home, s->fine_start, s->corr_ovf, s->tile_clear, s->tile_epoch, s->tile_closed, s->src_cell, s->src_lo, s->src_target, s->src_of, s->src_need, s->src_vel, s->src_slab.words, s->coerce_map, s->grid_flag, s->rank, s->vc_src, s->bkey, s->tile_count, s->tile_start, s->tile_flag, s->tile_scan, s->ptiles_all, s->dtiles, s->halo_tiles, s->dist_red,
 	                s->xbuf[0], s->xbuf[1], s->xbuf[2], s->xbuf[3],
 	                s->tile_pslot, s->scan_tmp, s->u, s->v, s->w, s->uo, s->vo, s->wo, s->ctype, s->solid,
 	                s->cell_count, s->stage, s->acc, s->abits, s->vp, s->vr, s->vz, s->vs, s->vpre, s->vq, s->vs2, s->c_as, s->nbr_table,
@@ -461,8 +461,7 @@ static int alloc_soa(lfa_sim *s, ParticleSoA &p, size_t cap) {
 	hipError_t e = hipMalloc(&p.base, cap * 17 * 4);
 	if (e != hipSuccess) return lfa_fail(s, LFA_E_OOM, "hipMalloc of particle SoA (%zu particles) failed", cap);
 	float *f = (float *)p.base;
-	p.key = (uint32_t *)f;
-	for (int k = 0; k < 3; ++k) p.t[k] = f + cap * (1 + k);
+	p.pos = (PosRec *)f;  // (cap is a multiple of 1024: every array starts 16-byte aligned)
 	for (int k = 0; k < 3; ++k) p.v[k] = f + cap * (4 + k);
 	for (int k = 0; k < 9; ++k) p.c[k] = f + cap * (7 + k);
 	p.id = (uint32_t *)(f + cap * 16);
@@ -476,26 +475,30 @@ int lfa_particles_alloc(lfa_sim *s, size_t n) {
 	LFA_HIP(s, hipStreamSynchronize(s->stream));
 	const size_t cap = (n + 1023) & ~(size_t)1023;
 	ParticleSoA nb[2];
-	uint32_t *rank = nullptr, *vc_src = nullptr;
+	uint32_t *rank = nullptr, *vc_src = nullptr, *bkey = nullptr;
 	int rc = alloc_soa(s, nb[0], cap);
 	if (rc == LFA_OK) rc = alloc_soa(s, nb[1], cap);
 	if (rc == LFA_OK && hipMalloc(&rank, cap * 4) != hipSuccess) rc = lfa_fail(s, LFA_E_OOM, "hipMalloc of the rank array failed");
 	if (rc == LFA_OK && hipMalloc(&vc_src, cap * 4) != hipSuccess) rc = lfa_fail(s, LFA_E_OOM, "hipMalloc of the source-index array failed");
+	if (rc == LFA_OK && hipMalloc(&bkey, cap * 4) != hipSuccess) rc = lfa_fail(s, LFA_E_OOM, "hipMalloc of the binned-key array failed");
 	if (rc != LFA_OK) {
 		free_soa(nb[0]);
 		free_soa(nb[1]);
 		if (rank) (void)hipFree(rank);
 		if (vc_src) (void)hipFree(vc_src);
+		if (bkey) (void)hipFree(bkey);
 		return rc;
 	}
 	free_soa(s->pb[0]);
 	free_soa(s->pb[1]);
 	if (s->rank) (void)hipFree(s->rank);
 	if (s->vc_src) (void)hipFree(s->vc_src);
+	if (s->bkey) (void)hipFree(s->bkey);
 	s->pb[0] = nb[0];
 	s->pb[1] = nb[1];
 	s->rank = rank;
 	s->vc_src = vc_src;
+	s->bkey = bkey;
 	s->vc_pending = false;
 	s->pcap = cap;
 	return LFA_OK;
@@ -521,12 +524,11 @@ int lfa_particles_reserve(lfa_sim *s, size_t n_keep, size_t n_total) {
 	ParticleSoA &dst = s->pb[s->cur];
 	const uint32_t *src_arrays[17];
 	uint32_t *dst_arrays[17];
-	src_arrays[0] = keep.key; dst_arrays[0] = dst.key;
-	for (int k = 0; k < 3; ++k) { src_arrays[1 + k] = (uint32_t *)keep.t[k]; dst_arrays[1 + k] = (uint32_t *)dst.t[k]; }
+	if (n_keep) LFA_HIP(s, hipMemcpyAsync(dst.pos, keep.pos, n_keep * sizeof(PosRec), hipMemcpyDeviceToDevice, s->stream));
 	for (int k = 0; k < 3; ++k) { src_arrays[4 + k] = (uint32_t *)keep.v[k]; dst_arrays[4 + k] = (uint32_t *)dst.v[k]; }
 	for (int k = 0; k < 9; ++k) { src_arrays[7 + k] = (uint32_t *)keep.c[k]; dst_arrays[7 + k] = (uint32_t *)dst.c[k]; }
 	src_arrays[16] = keep.id; dst_arrays[16] = dst.id;
-	for (int a = 0; a < 17; ++a)
+	for (int a = 4; a < 17; ++a)
 		if (n_keep) LFA_HIP(s, hipMemcpyAsync(dst_arrays[a], src_arrays[a], n_keep * 4, hipMemcpyDeviceToDevice, s->stream));
 	LFA_HIP(s, hipStreamSynchronize(s->stream));
 	free_soa(keep);
@@ -543,12 +545,9 @@ __global__ void k_ingest(const double *aos, size_t n, ParticleSoA p, GridDims g,
 	cell_and_fraction(q[1], ip.off[1], ip.h, g.ny, c[1], t[1]);
 	cell_and_fraction(q[2], ip.off[2], ip.h, g.nz, c[2], t[2]);
 	// a particle outside this rank's tile layers belongs to another rank: dropped by the binning (key = invalid)
-	p.key[i] = ((c[2] >> 3) >= slab_lo && (c[2] >> 3) < slab_hi) ? blocked_index(g, c[0], c[1], c[2]) : 0xFFFFFFFFu;
+	pos_store(p.pos, i, ((c[2] >> 3) >= slab_lo && (c[2] >> 3) < slab_hi) ? blocked_index(g, c[0], c[1], c[2]) : 0xFFFFFFFFu, t[0], t[1], t[2]);
 #pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		p.t[k][i] = t[k];
-		p.v[k][i] = (float)q[3 + k];
-	}
+	for (int k = 0; k < 3; ++k) p.v[k][i] = (float)q[3 + k];
 #pragma unroll
 	for (int k = 0; k < 9; ++k) p.c[k][i] = (float)q[6 + k];
 	p.id[i] = (uint32_t)i;
@@ -585,35 +584,37 @@ extern "C" int lfa_upload_particles(lfa_sim *s, const void *aos152, uint64_t n) 
 
 /// Slabs after a hand-over: valid[i] = record i is a resident particle (not one that went to a neighbour rank); its exclusive
 /// scan is the record's slot in a download, so holes never reach the host - and no binning (a collective on slabs) is needed.
-__global__ void k_valid_flags(const uint32_t *key, size_t n, uint32_t *valid) {
+__global__ void k_valid_flags(const PosRec *pos, size_t n, uint32_t *valid) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) valid[i] = key[i] != 0xFFFFFFFFu ? 1u : 0u;
+	if (i < n) valid[i] = pos[i].key != 0xFFFFFFFFu ? 1u : 0u;
 }
-__global__ void k_export_ids(const uint32_t *key, const uint32_t *id, const uint32_t *slot, size_t n, uint32_t *out) {
+__global__ void k_export_ids(const PosRec *pos, const uint32_t *id, const uint32_t *slot, size_t n, uint32_t *out) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n && key[i] != 0xFFFFFFFFu) out[slot ? slot[i] : i] = id[i];
+	if (i < n && pos[i].key != 0xFFFFFFFFu) out[slot ? slot[i] : i] = id[i];
 }
 
 /// `old`: lfa_advect / lfa_correct have moved the particles and lfa_collide is still due - old_position is the position of before
-/// the move (what a host callback between the two stages sees in the reference), kept in old.key / old.t.
+/// the move (what a host callback between the two stages sees in the reference), kept in old.pos.
 __global__ void k_export(double *aos, size_t n, ParticleSoA p, GridDims g, IngestParams ip, int flags, int by_slot, const uint32_t *slot,
                          ParticleSoA old, int have_old, const float *c_home, size_t c_home_stride) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	uint32_t b = p.key[i];
+	const PosRec me = pos_load(p.pos, i);
+	const uint32_t b = me.key;
 	if (slot && b == 0xFFFFFFFFu) return;
 	// slab decomposition: particles migrate between ranks, so a rank's records come out in storage order (ids separately)
 	double *q = aos + (by_slot ? (slot ? (size_t)slot[i] : i) : (size_t)p.id[i]) * 19;
 	if (flags & LFA_DL_POSITIONS) {
 		double x[3];
-		particle_world_position(g, ip, b, p.t[0][i], p.t[1][i], p.t[2][i], x);
+		particle_world_position(g, ip, b, me.t[0], me.t[1], me.t[2], x);
 #pragma unroll
 		for (int k = 0; k < 3; ++k) {
 			q[k] = x[k];
 			q[15 + k] = x[k];
 		}
 		if (have_old) {
-			particle_world_position(g, ip, old.key[i], old.t[0][i], old.t[1][i], old.t[2][i], x);
+			const PosRec was = pos_load(old.pos, i);
+			particle_world_position(g, ip, was.key, was.t[0], was.t[1], was.t[2], x);
 #pragma unroll
 			for (int k = 0; k < 3; ++k) q[15 + k] = x[k];
 		}
@@ -630,7 +631,7 @@ __global__ void k_export(double *aos, size_t n, ParticleSoA p, GridDims g, Inges
 int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot) {
 	*slot = nullptr;
 	if (!s->dist || !s->holes || !s->np_live) return LFA_OK;
-	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((s->np_live + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->pb[s->cur].key,
+	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((s->np_live + 255) / 256)), dim3(256), 0, s->stream, (const PosRec *)s->pb[s->cur].pos,
 	                   s->np_live, s->rank);
 	LFA_LAUNCH_CHECK(s);
 	uint32_t *tot = (uint32_t *)(s->pcg_state + LFA_DW_SCAN_TOTAL);
@@ -647,22 +648,21 @@ int lfa_slab_download_slots(lfa_sim *s, const uint32_t **slot) {
 /// valid flags), whole, in storage order.
 __global__ void __launch_bounds__(256) k_close_holes(size_t n, ParticleSoA src, ParticleSoA dst, const uint32_t *slot, size_t n_dst) {
 	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-	if (i >= n || src.key[i] == 0xFFFFFFFFu) return;
+	if (i >= n) return;
+	const PosRec me = pos_load(src.pos, i);
+	if (me.key == 0xFFFFFFFFu) return;
 	const size_t d = slot[i];
 	if (d >= n_dst) return;  // (cannot happen: the caller has compared the scan's total with the resident count)
-	dst.key[d] = src.key[i];
+	pos_store(dst.pos, d, me.key, me.t[0], me.t[1], me.t[2]);
 #pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		dst.t[k][d] = src.t[k][i];
-		dst.v[k][d] = src.v[k][i];
-	}
+	for (int k = 0; k < 3; ++k) dst.v[k][d] = src.v[k][i];
 #pragma unroll
 	for (int k = 0; k < 9; ++k) dst.c[k][d] = src.c[k][i];
 	dst.id[d] = src.id[i];
 }
 
 int lfa_particles_close_holes(lfa_sim *s, size_t n_rec) {
-	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream, (const uint32_t *)s->pb[s->cur].key,
+	hipLaunchKernelGGL(k_valid_flags, dim3((unsigned)((n_rec + 255) >> 8)), dim3(256), 0, s->stream, (const PosRec *)s->pb[s->cur].pos,
 	                   n_rec, s->rank);
 	LFA_LAUNCH_CHECK(s);
 	size_t n_dst = 0;
@@ -722,7 +722,7 @@ extern "C" int lfa_download_particle_ids(lfa_sim *s, uint32_t *ids, uint64_t n) 
 	LFA_TRY(lfa_slab_download_slots(s, &slot));
 	if (slot) {
 		LFA_TRY(lfa_ensure_io(s, n * 4));
-		hipLaunchKernelGGL(k_export_ids, dim3((unsigned)((s->np_live + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t *)s->pb[s->cur].key,
+		hipLaunchKernelGGL(k_export_ids, dim3((unsigned)((s->np_live + 255) / 256)), dim3(256), 0, s->stream, (const PosRec *)s->pb[s->cur].pos,
 		                   (const uint32_t *)s->pb[s->cur].id, slot, s->np_live, (uint32_t *)s->io_buf);
 		LFA_LAUNCH_CHECK(s);
 		LFA_HIP(s, hipMemcpyAsync(ids, s->io_buf, n * 4, hipMemcpyDeviceToHost, s->stream));
@@ -761,12 +761,9 @@ __global__ void k_seed_block(size_t n, size_t first, ParticleSoA p, GridDims g, 
 		double pos = ip.off[a] + ((double)cell[a] + ((double)sb[a] + uu) * 0.5) * ip.h;
 		cell_and_fraction(pos, ip.off[a], ip.h, nn[a], c[a], t[a]);
 	}
-	p.key[j] = blocked_index(g, c[0], c[1], c[2]);
+	pos_store(p.pos, j, blocked_index(g, c[0], c[1], c[2]), t[0], t[1], t[2]);
 #pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		p.t[k][j] = t[k];
-		p.v[k][j] = 0.0f;
-	}
+	for (int k = 0; k < 3; ++k) p.v[k][j] = 0.0f;
 	particle_zero_c_set_id(p, j, (uint32_t)(global_ids ? i : j));
 }
 
@@ -927,8 +924,9 @@ extern "C" int lfa_upload_cells(lfa_sim *s, const void *aos32) {
 /// issues one atomic per distinct tile among them: particles arrive tile-coherent (they were binned last step and move < 1
 /// tile), so that is 1-3 atomics per 256 particles, and a wave's particles of one tile get consecutive ranks in input order
 /// (the scatter then writes runs of up to 1 KB per field). One particle per lane spent its time waiting for the returning
-/// atomic (0.54 ms at C4; 4 chunks: see DESIGN.md).
-__global__ void __launch_bounds__(256) k_tile_count(const uint32_t *key, size_t n, uint32_t *tile_count, uint32_t *rank) {
+/// atomic (0.54 ms at C4; 4 chunks: see DESIGN.md). The keys come out of the position records, a 4-byte read at a 16-byte stride:
+/// this kernel runs only where no advection has ranked the particles on its way (lfa_hash_particles on its own, lfa_step_hot).
+__global__ void __launch_bounds__(256) k_tile_count(const PosRec *pos, size_t n, uint32_t *tile_count, uint32_t *rank) {
 	const int lane = threadIdx.x & 63;
 	const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const size_t i0 = wave * (64 * TC_CHUNKS) + lane;
@@ -936,7 +934,7 @@ __global__ void __launch_bounds__(256) k_tile_count(const uint32_t *key, size_t 
 #pragma unroll
 	for (int c = 0; c < TC_CHUNKS; ++c) {
 		const size_t i = i0 + 64 * c;
-		const uint32_t k = i < n ? key[i] : 0xFFFFFFFFu;
+		const uint32_t k = i < n ? pos[i].key : 0xFFFFFFFFu;
 		tile[c] = k != 0xFFFFFFFFu ? k >> 9 : 0xFFFFFFFFu;
 	}
 	lfa_wave_tile_ranks(tile, tile_count, my_rank);
@@ -976,36 +974,37 @@ __global__ void k_dilate(const int *ptiles, int n_ptiles, uint32_t *flag, GridDi
 /// Pass 2: move every particle to its tile's segment. With `shuffle` the slot inside the segment is a multiplicative
 /// permutation of the rank, which separates particles of one cell (uploads arrive cell-sorted; neighbouring lanes
 /// hitting one cell would serialise the LDS atomics of the P2G scatter).
-/// Only key, t, id move (20 of the 68 bytes); from[d] records the source index, v and C follow through it (k_p2g_binned,
+/// Only the position record and the id move (20 of the 68 bytes), the key once more on its own into bkey, for the cell count that
+/// follows (keys out of the records would be four times its bytes); from[d] records the source index, v and C follow through it (k_p2g_binned,
 /// k_g2p, k_gather_vc) - see lfa_sim::vc_pending. (PIC / FLIP keep C in its home array, indexed by the particle id.)
 __global__ void k_tile_scatter(size_t n, ParticleSoA src, ParticleSoA dst, const uint32_t *rank,
-                               const uint32_t *tile_start, const uint32_t *tile_count, int shuffle, uint32_t *from) {
+                               const uint32_t *tile_start, const uint32_t *tile_count, int shuffle, uint32_t *from, uint32_t *bkey) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	uint32_t key = src.key[i], tile = key >> 9, r = rank[i];
+	const PosRec me = pos_load(src.pos, i);
+	uint32_t key = me.key, tile = key >> 9, r = rank[i];
 	if (key == 0xFFFFFFFFu) return;
 	if (shuffle) {
 		uint32_t cnt = tile_count[tile];
 		if (cnt % 1000003u != 0) r = (uint32_t)(((uint64_t)r * 1000003ull) % cnt);
 	}
 	size_t d = (size_t)tile_start[tile] + r;
-	dst.key[d] = key;
-#pragma unroll
-	for (int k = 0; k < 3; ++k) dst.t[k][d] = src.t[k][i];
+	pos_store(dst.pos, d, key, me.t[0], me.t[1], me.t[2]);
+	bkey[d] = key;
 	dst.id[d] = src.id[i];
 	from[d] = (uint32_t)i;
 }
 /// C to / from its home array (indexed by particle id): see lfa_sim::c_home.
 __global__ void k_c_to_home(size_t n, ParticleSoA p, float *home, size_t stride) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n || p.key[i] == 0xFFFFFFFFu) return;
+	if (i >= n || p.pos[i].key == 0xFFFFFFFFu) return;
 	const size_t j = p.id[i];
 #pragma unroll
 	for (int k = 0; k < 9; ++k) home[k * stride + j] = p.c[k][i];
 }
 __global__ void k_c_from_home(size_t n, ParticleSoA p, const float *home, size_t stride) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n || p.key[i] == 0xFFFFFFFFu) return;
+	if (i >= n || p.pos[i].key == 0xFFFFFFFFu) return;
 	const size_t j = p.id[i];
 #pragma unroll
 	for (int k = 0; k < 9; ++k) p.c[k][i] = home[k * stride + j];
@@ -1164,7 +1163,7 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 	if (!counts_done) {
 		LFA_HIP(s, hipMemsetAsync(s->tile_count, 0, (size_t)(nt + 1) * 4, s->stream));
 		if (n) {
-			hipLaunchKernelGGL(k_tile_count, dim3((unsigned)((n + 256 * TC_CHUNKS - 1) / (256 * TC_CHUNKS))), dim3(256), 0, s->stream, src.key, n,
+			hipLaunchKernelGGL(k_tile_count, dim3((unsigned)((n + 256 * TC_CHUNKS - 1) / (256 * TC_CHUNKS))), dim3(256), 0, s->stream, (const PosRec *)src.pos, n,
 			                   s->tile_count, s->rank);
 			LFA_LAUNCH_CHECK(s);
 		}
@@ -1261,7 +1260,7 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 		// (an upload arrives cell-sorted: the first binning permutes the slots inside a tile so that neighbouring lanes of the P2G
 		// do not hit one cell)
 		hipLaunchKernelGGL(k_tile_scatter, sgrid, dim3(256), 0, s->stream, n, src, dst, s->rank, s->tile_start, s->tile_count,
-		                   s->binned ? 0 : 1, s->vc_src);
+		                   s->binned ? 0 : 1, s->vc_src, s->bkey);
 		LFA_LAUNCH_CHECK(s);
 		s->cur ^= 1;
 		s->vc_pending = true;
@@ -1271,7 +1270,7 @@ int lfa_hash_particles_impl(lfa_sim *s, bool counts_done) {
 	if (s->n_dtiles) {
 		int grid = s->n_dtiles < 8192 ? s->n_dtiles : 8192;
 		hipLaunchKernelGGL(k_cell_count, dim3(grid), dim3(256), 0, s->stream, s->dtiles, s->n_dtiles,
-		                   s->pb[s->cur].key, s->tile_start, s->cell_count);
+		                   (const uint32_t *)s->bkey, s->tile_start, s->cell_count);
 		LFA_LAUNCH_CHECK(s);
 	}
 	s->binned = true;

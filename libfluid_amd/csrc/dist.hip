@@ -357,7 +357,7 @@ k_pack_leavers(size_t n, ParticleSoA p, int tiles_per_layer, int slab_lo, int sl
 	int dest = -1;
 	uint32_t key = 0xFFFFFFFFu;
 	if (i < n) {
-		key = p.key[i];
+		key = p.pos[i].key;
 		if (key != 0xFFFFFFFFu) {
 			const int tz = (int)(key >> 9) / tiles_per_layer;
 			dest = tz < slab_lo ? 0 : (tz >= slab_hi ? 1 : -1);
@@ -379,7 +379,7 @@ k_pack_leavers(size_t n, ParticleSoA p, int tiles_per_layer, int slab_lo, int sl
 			const size_t j = from ? (size_t)from[i] : i;
 #pragma unroll
 			for (int k = 0; k < 3; ++k) {
-				rec[1 + k] = __float_as_uint(p.t[k][i]);
+				rec[1 + k] = __float_as_uint(p.pos[i].t[k]);
 				rec[4 + k] = __float_as_uint(from ? pvc.v[k][j] : p.v[k][i]);
 			}
 #pragma unroll
@@ -387,7 +387,7 @@ k_pack_leavers(size_t n, ParticleSoA p, int tiles_per_layer, int slab_lo, int sl
 				rec[7 + k] = __float_as_uint(c_home ? c_home[k * c_home_stride + p.id[i]]  // (lfa_sim::c_home)
 				                                    : (from && c_deferred ? pvc.c[k][j] : p.c[k][i]));
 			rec[16] = p.id[i];
-			p.key[i] = 0xFFFFFFFFu;
+			p.pos[i].key = 0xFFFFFFFFu;
 		}
 	}
 }
@@ -403,12 +403,9 @@ __global__ void __launch_bounds__(256) k_unpack_arrivals(size_t n, const uint32_
 	const uint32_t *rec = buf + i * 17;
 	const size_t d = at + i, e = from ? ext + i : d;
 	const ParticleSoA &q = from ? pvc : p;
-	p.key[d] = rec[0];
+	pos_store(p.pos, d, rec[0], __uint_as_float(rec[1]), __uint_as_float(rec[2]), __uint_as_float(rec[3]));
 #pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		p.t[k][d] = __uint_as_float(rec[1 + k]);
-		q.v[k][e] = __uint_as_float(rec[4 + k]);
-	}
+	for (int k = 0; k < 3; ++k) q.v[k][e] = __uint_as_float(rec[4 + k]);
 #pragma unroll
 	for (int k = 0; k < 9; ++k) {
 		if (c_home) c_home[k * c_home_stride + rec[16]] = __uint_as_float(rec[7 + k]);
@@ -532,10 +529,10 @@ int lfa_dist_exchange_ghost_particles(lfa_sim *s) {
 	const size_t send_lo_at = hs[0], send_lo_n = lfa_has_lo(s) ? hs[1] - hs[0] : 0;
 	const size_t send_hi_at = hs[2], send_hi_n = lfa_has_hi(s) ? hs[3] - hs[2] : 0;
 	// key, in-cell position and the global id (the mesher orders the particles of a cell by it)
-	uint32_t *arr[5] = {p.key, (uint32_t *)p.t[0], (uint32_t *)p.t[1], (uint32_t *)p.t[2], p.id};
-	for (int a = 0; a < 5; ++a)
-		LFA_TRY(s->dist->exchange(s, arr[a] + send_lo_at, send_lo_n * 4, arr[a] + at_lo, n_g[0] * 4, arr[a] + send_hi_at,
-		                          send_hi_n * 4, arr[a] + at_hi, n_g[1] * 4));
+	LFA_TRY(s->dist->exchange(s, p.pos + send_lo_at, send_lo_n * sizeof(PosRec), p.pos + at_lo, n_g[0] * sizeof(PosRec), p.pos + send_hi_at,
+	                          send_hi_n * sizeof(PosRec), p.pos + at_hi, n_g[1] * sizeof(PosRec)));
+	LFA_TRY(s->dist->exchange(s, p.id + send_lo_at, send_lo_n * 4, p.id + at_lo, n_g[0] * 4, p.id + send_hi_at, send_hi_n * 4, p.id + at_hi,
+	                          n_g[1] * 4));
 	s->ghost_at[0] = at_lo;
 	s->ghost_at[1] = at_hi;
 	s->n_ghost_particles = n_g[0] + n_g[1];

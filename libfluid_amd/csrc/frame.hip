@@ -119,15 +119,15 @@ struct FrameParams {
 /// The pass: records [0, n) of the current buffer (slabs: a record handed to a neighbour rank carries an invalid key and is no
 /// particle of this rank). OCC: also count into occupation[nx ny nz], x fastest; n_in_grid is counted either way.
 template <bool OCC>
-__global__ void __launch_bounds__(256) k_frame_stats(size_t n, const uint32_t *key, const float *t0, const float *t1, const float *t2,
-                                                     const float *v0, const float *v1, const float *v2, GridDims g, FrameParams q,
+__global__ void __launch_bounds__(256) k_frame_stats(size_t n, const PosRec *pos, const float *v0, const float *v1, const float *v2, GridDims g, FrameParams q,
                                                      uint32_t *occupation, double *part) {
 	FrameAcc a = frame_neutral();
 	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-		const uint32_t b = key[i];
+		const PosRec me = pos_load(pos, i);
+		const uint32_t b = me.key;
 		if (b == 0xFFFFFFFFu) continue;
 		double x[3];
-		particle_world_position(g, q.ip, b, t0[i], t1[i], t2[i], x);
+		particle_world_position(g, q.ip, b, me.t[0], me.t[1], me.t[2], x);
 		const double vx = (double)v0[i], vy = (double)v1[i], vz = (double)v2[i];
 		double sq = vx * vx;
 		sq += vy * vy;
@@ -169,17 +169,17 @@ __global__ void __launch_bounds__(256) k_frame_finish(int n_part, double *part) 
 }
 
 /// double[3] per particle, in the order of a download: single domain by particle id, slabs by storage slot (holes closed).
-__global__ void __launch_bounds__(256) k_export_positions(double *xyz, size_t n, size_t n_out, const uint32_t *key, const float *t0,
-                                                          const float *t1, const float *t2, const uint32_t *id, GridDims g, IngestParams ip,
+__global__ void __launch_bounds__(256) k_export_positions(double *xyz, size_t n, size_t n_out, const PosRec *pos, const uint32_t *id, GridDims g, IngestParams ip,
                                                           int by_slot, const uint32_t *slot) {
 	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
-	const uint32_t b = key[i];
+	const PosRec me = pos_load(pos, i);
+	const uint32_t b = me.key;
 	if (b == 0xFFFFFFFFu) return;
 	const size_t d = by_slot ? (slot ? (size_t)slot[i] : i) : (size_t)id[i];
 	if (d >= n_out) return;  // (cannot happen: ids and slots are below the resident count; keeps the write inside the buffer regardless)
 	double x[3];
-	particle_world_position(g, ip, b, t0[i], t1[i], t2[i], x);
+	particle_world_position(g, ip, b, me.t[0], me.t[1], me.t[2], x);
 #pragma unroll
 	for (int k = 0; k < 3; ++k) xyz[3 * d + k] = x[k];
 }
@@ -227,12 +227,12 @@ extern "C" int lfa_frame_stats(lfa_sim *s, struct lfa_frame_stats *out, uint32_t
 	LFA_HIP(s, hipEventRecord(s->frame_ev[0], s->stream));
 	if (occupation) {
 		LFA_HIP(s, hipMemsetAsync(s->io_buf, 0, s->nc * 4, s->stream));
-		hipLaunchKernelGGL(k_frame_stats<true>, dim3((unsigned)blocks), dim3(256), 0, s->stream, n_rec, (const uint32_t *)p.key,
-		                   (const float *)p.t[0], (const float *)p.t[1], (const float *)p.t[2], (const float *)p.v[0], (const float *)p.v[1],
+		hipLaunchKernelGGL(k_frame_stats<true>, dim3((unsigned)blocks), dim3(256), 0, s->stream, n_rec, (const PosRec *)p.pos,
+		                   (const float *)p.v[0], (const float *)p.v[1],
 		                   (const float *)p.v[2], s->g, q, (uint32_t *)s->io_buf, s->frame_part);
 	} else {
-		hipLaunchKernelGGL(k_frame_stats<false>, dim3((unsigned)blocks), dim3(256), 0, s->stream, n_rec, (const uint32_t *)p.key,
-		                   (const float *)p.t[0], (const float *)p.t[1], (const float *)p.t[2], (const float *)p.v[0], (const float *)p.v[1],
+		hipLaunchKernelGGL(k_frame_stats<false>, dim3((unsigned)blocks), dim3(256), 0, s->stream, n_rec, (const PosRec *)p.pos,
+		                   (const float *)p.v[0], (const float *)p.v[1],
 		                   (const float *)p.v[2], s->g, q, (uint32_t *)nullptr, s->frame_part);
 	}
 	LFA_LAUNCH_CHECK(s);
@@ -284,7 +284,7 @@ extern "C" int lfa_download_positions(lfa_sim *s, double *xyz, uint64_t n) {
 	const size_t n_rec = s->binned ? s->np_live : s->np;
 	const ParticleSoA &p = s->pb[s->cur];
 	hipLaunchKernelGGL(k_export_positions, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s->stream, (double *)s->io_buf, n_rec,
-	                   (size_t)n, (const uint32_t *)p.key, (const float *)p.t[0], (const float *)p.t[1], (const float *)p.t[2],
+	                   (size_t)n, (const PosRec *)p.pos,
 	                   (const uint32_t *)p.id, s->g, ip, s->dist ? 1 : 0, slot);
 	LFA_LAUNCH_CHECK(s);
 	LFA_HIP(s, hipMemcpyAsync(xyz, s->io_buf, n * 24, hipMemcpyDeviceToHost, s->stream));

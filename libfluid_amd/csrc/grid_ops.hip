@@ -364,7 +364,8 @@ __device__ inline void g2p_store(const ParticleSoA &p, uint32_t i, const float (
 template <int METHOD, typename Corner, typename Fetch>
 __device__ inline float g2p_particle(const ParticleSoA &p, uint32_t i, const ParticleSoA &pold, uint32_t j, const G2PParams &gp,
                                     Corner &&corner, Fetch &&fetch) {
-	const float t[3] = {p.t[0][i], p.t[1][i], p.t[2][i]};
+	const PosRec me = pos_load(p.pos, i);
+	const float t[3] = {me.t[0], me.t[1], me.t[2]};
 	float vp[3] = {0.0f, 0.0f, 0.0f}, vout[3], cvec[9];
 	if (METHOD == LFA_FLIP_BLEND) {
 #pragma unroll
@@ -455,10 +456,11 @@ k_g2p(const int *ptiles, int n_ptiles, GridDims g, ParticleSoA p, const uint32_t
 			float t[3], vp[3];
 		} cur, nxt;
 		auto load = [&](uint32_t i, uint32_t j, Regs &r) {
-			r.key = p.key[i];
+			const PosRec me = pos_load(p.pos, i);
+			r.key = me.key;
 #pragma unroll
 			for (int k = 0; k < 3; ++k) {
-				r.t[k] = p.t[k][i];
+				r.t[k] = me.t[k];
 				r.vp[k] = FLIP ? pold.v[k][j] : 0.0f;
 			}
 		};
@@ -536,7 +538,7 @@ k_g2p_leavers(GridDims g, ParticleSoA p, const float *u, const float *v, const f
 	const uint32_t n = *n_leavers;
 	float vmax2 = 0.0f;
 	for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
-		const uint32_t i = leavers[k], key = p.key[i];
+		const uint32_t i = leavers[k], key = p.pos[i].key;
 		if (key == 0xFFFFFFFFu) continue;
 		const int tile = (int)(key >> 9), l = (int)(key & 511);
 		int tx, ty, tz;

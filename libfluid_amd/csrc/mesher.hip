@@ -768,7 +768,8 @@ __global__ void k_sim_positions(ParticleSoA p, size_t first, size_t n, size_t ou
 	const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (k >= n) return;
 	const size_t i = first + k;
-	const uint32_t b = p.key[i];
+	const PosRec me = pos_load(p.pos, i);
+	const uint32_t b = me.key;
 	const int tile = (int)(b >> 9), l = (int)(b & 511);
 	int tx, ty, tz;
 	tile_coords(g, tile, tx, ty, tz);
@@ -779,7 +780,7 @@ __global__ void k_sim_positions(ParticleSoA p, size_t first, size_t n, size_t ou
 	const size_t at = by_slot ? out_at + k : (size_t)p.id[i];
 	double *q = pos + 3 * at;
 #pragma unroll
-	for (int d = 0; d < 3; ++d) q[d] = off[d] + ((double)c[d] + (double)p.t[d][i]) * h;
+	for (int d = 0; d < 3; ++d) q[d] = off[d] + ((double)c[d] + (double)me.t[d]) * h;
 	if (by_slot) ids[at] = p.id[i];
 }
 

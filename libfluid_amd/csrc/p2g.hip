@@ -184,10 +184,11 @@ struct ParticleRegs {
 /// pvc == p and j == i).
 template <bool APIC>
 __device__ inline void load_particle(const ParticleSoA &p, const ParticleSoA &pvc, uint32_t i, uint32_t j, ParticleRegs &r) {
-	r.key = p.key[i];
+	const PosRec me = pos_load(p.pos, i);
+	r.key = me.key;
 #pragma unroll
 	for (int k = 0; k < 3; ++k) {
-		r.t[k] = p.t[k][i];
+		r.t[k] = me.t[k];
 		r.v[k] = pvc.v[k][j];
 	}
 	if (APIC) {
@@ -259,12 +260,13 @@ __global__ void __launch_bounds__(256)
 k_p2g_atomic(size_t n, ParticleSoA p, float *acc, size_t ncp, GridDims g, float hworld) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const uint32_t key = p.key[i];
+	const PosRec me = pos_load(p.pos, i);
+	const uint32_t key = me.key;
 	const int tile = (int)(key >> 9), l = (int)(key & 511);
 	int tx, ty, tz;
 	tile_coords(g, tile, tx, ty, tz);
 	const int cx = tx * 8 + (l & 7), cy = ty * 8 + ((l >> 3) & 7), cz = tz * 8 + (l >> 6);
-	float t[3] = {p.t[0][i], p.t[1][i], p.t[2][i]};
+	float t[3] = {me.t[0], me.t[1], me.t[2]};
 	float v[3] = {p.v[0][i], p.v[1][i], p.v[2][i]};
 	float c[9];
 	if (APIC) {

@@ -184,10 +184,11 @@ struct AdvectSlot {
 /// Load phase, first round trip: what does not depend on the key. Unconditional: the caller clamps an index >= n to a valid one
 /// and marks the slot invalid afterwards; the values of an invalid slot are never used.
 __device__ inline void advect_load(size_t i, const ParticleSoA &p, AdvectSlot &a) {
-	a.key = p.key[i];
+	const PosRec me = pos_load(p.pos, i);
+	a.key = me.key;
 #pragma unroll
 	for (int d = 0; d < 3; ++d) {
-		a.t[d] = p.t[d][i];
+		a.t[d] = me.t[d];
 		a.v[d] = p.v[d][i];
 	}
 }
@@ -239,14 +240,12 @@ __device__ inline uint32_t advect_move(AdvectSlot &a, const GridDims &g, const u
 	a.key = blocked_index(g, nc[0], nc[1], nc[2]);
 	return a.key;
 }
-/// Store phase: key and fractions of a valid slot; of a coerced one the source's velocity and C = 0 as well (rare: its id load
+/// Store phase: the position record of a valid slot; of a coerced one the source's velocity and C = 0 as well (rare: its id load
 /// is the one load that follows a store).
 template <bool COERCE>
 __device__ inline void advect_store(size_t i, const ParticleSoA &p, const MoveParams &mp, const AdvectSlot &a) {
 	if (a.key == 0xFFFFFFFFu) return;
-	p.key[i] = a.key;
-#pragma unroll
-	for (int d = 0; d < 3; ++d) p.t[d][i] = a.t[d];
+	pos_store(p.pos, i, a.key, a.t[0], a.t[1], a.t[2]);
 	if (COERCE && a.src) {
 #pragma unroll
 		for (int d = 0; d < 3; ++d) p.v[d][i] = a.v[d];
@@ -390,9 +389,8 @@ __device__ inline void fine_decode(const float4 &r, int fy, int fz, float t[3], 
 
 /// Per particle tile: its particles grouped by fine cell - fine_start[tile][f] = first record of fine cell f (absolute), records
 /// (fine_record) in spos. (What the reference's _space_hash is to its 27-cell walk, include/fluid/simulation.h:193-197.)
-__global__ void __launch_bounds__(FIDX_THREADS)
-k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const float *t0, const float *t1, const float *t2,
-                   const uint32_t *tile_start, const uint32_t *tile_count, uint32_t *fine_start, float4 *spos, uint32_t *key_copy) {
+__global__ void __launch_bounds__(FIDX_THREADS, 4)  // (128 VGPRs: two workgroups per CU, what the LDS allows)
+k_build_fine_index(const int *ptiles, int n_ptiles, const PosRec *pos, const uint32_t *tile_start, const uint32_t *tile_count, uint32_t *fine_start, float4 *spos, uint32_t *key_copy) {
 	// Counters and cursors are relative to the tile's first record. A tile that fits the staging area has at most FIDX_STAGE < 2^16
 	// records: its counters are 16 bits wide, two per word (an atomic add on the word bumps one half; a cursor ends at the next
 	// cell's start, so the low half never carries into the high one) - the 2 663 of them take the room the 1 332 whole-cell words
@@ -406,9 +404,10 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 	constexpr int PER = FIDX_CNT / FIDX_THREADS;
 	uint32_t *cnt_big = (uint32_t *)stage;
 	auto fine_of = [&](uint32_t i, int l[3], float t[3]) -> int {
-		const uint32_t k = key[i];
+		const PosRec me = pos_load(pos, i);
+		const uint32_t k = me.key;
 		l[0] = (int)(k & 7); l[1] = (int)((k >> 3) & 7); l[2] = (int)((k >> 6) & 7);
-		t[0] = t0[i]; t[1] = t1[i]; t[2] = t2[i];
+		t[0] = me.t[0]; t[1] = me.t[1]; t[2] = me.t[2];
 		return fine_coord_x(l[0], t[0]) + FTX * (fine_coord(l[1], t[1]) + FT * fine_coord(l[2], t[2]));
 	};
 	constexpr int RPT = FIDX_STAGE / FIDX_THREADS;  // particles per thread of a tile that fits the staging area: kept in registers
@@ -436,8 +435,9 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 #pragma unroll
 			for (int r = 0; r < RPT; ++r) {
 				const uint32_t i = min(b + threadIdx.x + FIDX_THREADS * r, last);
-				rf[r] = key[i];
-				r0[r] = t0[i]; r1[r] = t1[i]; r2[r] = t2[i];
+				const PosRec me = pos_load(pos, i);
+				rf[r] = me.key;
+				r0[r] = me.t[0]; r1[r] = me.t[1]; r2[r] = me.t[2];
 			}
 #pragma unroll
 			for (int r = 0; r < RPT; ++r) {
@@ -518,7 +518,7 @@ k_build_fine_index(const int *ptiles, int n_ptiles, const uint32_t *key, const f
 				float t[3];
 				const uint32_t at = atomicAdd(&cnt_big[fine_of(i, l, t)], 1u);
 				spos[b + at] = fine_record(l[0], l[1], l[2], t[0], t[1], t[2], i);
-				if (key_copy) key_copy[i] = key[i];
+				if (key_copy) key_copy[i] = pos[i].key;
 			}
 		}
 		__syncthreads();
@@ -538,13 +538,12 @@ __device__ inline int fine_source(const GridDims &g, const uint32_t *tile_count,
 }
 
 /// One record of the fallback pass below.
-__device__ inline void correct_collide_record(size_t rk, const ParticleSoA &p, uint32_t *out_key, float *out_tx, float *out_ty, float *out_tz,
-                                              const GridDims &g, const uint8_t *solid, const uint32_t *tile_count, const uint32_t *fine_start,
+__device__ inline void correct_collide_record(size_t rk, const ParticleSoA &p, PosRec *out, const GridDims &g, const uint8_t *solid, const uint32_t *tile_count, const uint32_t *fine_start,
                                               const float4 *spos, const MoveParams &mp, const uint32_t *only_flagged, const int *tile_pslot,
                                               int p_off, const uint32_t *key_before) {
 	const float4 me = spos[rk];
 	const size_t i = __float_as_uint(me.w);
-	const uint32_t key_i = key_before ? key_before[i] : p.key[i];
+	const uint32_t key_i = key_before ? key_before[i] : p.pos[i].key;
 	if (key_i == 0xFFFFFFFFu) return;
 	const int tile = (int)(key_i >> 9);
 	const int l[3] = {(int)(key_i & 7), (int)((key_i >> 3) & 7), (int)((key_i >> 6) & 7)};
@@ -607,15 +606,14 @@ __device__ inline void correct_collide_record(size_t rk, const ParticleSoA &p, u
 	float ntt[3];
 #pragma unroll
 	for (int d = 0; d < 3; ++d) split_position(to[d], nn[d], nc[d], ntt[d]);
-	out_key[i] = blocked_index(g, nc[0], nc[1], nc[2]);
-	out_tx[i] = ntt[0]; out_ty[i] = ntt[1]; out_tz[i] = ntt[2];
+	pos_store(out, i, blocked_index(g, nc[0], nc[1], nc[2]), ntt[0], ntt[1], ntt[2]);
 }
 
 /// _correct_positions + _detect_collisions for the particles of the flagged half tiles (those the LDS-tiled kernel could not
 /// hold) - or, without a flag bitmap, of all: a thread per particle gathers its 27 fine cells from the index in global memory.
 /// `n` = live particles = records of the owned tiles (ghost tiles' records lie behind them).
 __global__ void __launch_bounds__(256)
-k_correct_collide(size_t n, ParticleSoA p, uint32_t *out_key, float *out_tx, float *out_ty, float *out_tz, GridDims g,
+k_correct_collide(size_t n, ParticleSoA p, PosRec *out, GridDims g,
                    const uint8_t *solid, const uint32_t *tile_count, const uint32_t *fine_start, const float4 *spos, MoveParams mp,
                    const uint32_t *only_flagged, const int *tile_pslot, int p_off, const uint32_t *key_before) {
 	// A thread per RECORD of the index: everything about the particle as it was BEFORE the correction - the tiled kernel has
@@ -624,7 +622,7 @@ k_correct_collide(size_t n, ParticleSoA p, uint32_t *out_key, float *out_tx, flo
 	if (only_flagged && only_flagged[0] == 0) return;  // (word 0 counts the flagged parts: none, as a rule - the grid is bounded, so that
 	                                                     // costs a few thousand workgroups, not n / 256)
 	for (size_t rk = (size_t)blockIdx.x * blockDim.x + threadIdx.x; rk < n; rk += (size_t)gridDim.x * blockDim.x)
-		correct_collide_record(rk, p, out_key, out_tx, out_ty, out_tz, g, solid, tile_count, fine_start, spos, mp, only_flagged, tile_pslot,
+		correct_collide_record(rk, p, out, g, solid, tile_count, fine_start, spos, mp, only_flagged, tile_pslot,
 		                       p_off, key_before);
 }
 
@@ -653,7 +651,7 @@ __device__ unsigned long long g_corr_prof[8];
 // tests/test_kernel_budgets.py reads the figures from the compiler's metadata.)
 template <int CAP, bool ONLY>
 __global__ void __launch_bounds__(ONLY ? CORR_THREADS_BIG : CORR_THREADS, 4)
-k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx, float *out_ty, float *out_tz, GridDims g,
+k_correct_fine(const int *ptiles, int n_ptiles, PosRec *out, GridDims g,
                 const uint8_t *solid, const uint32_t *tile_count, const uint32_t *fine_start, const float4 *spos, MoveParams mp,
                 uint32_t *overflow_tiles, const uint8_t *tile_clear, const uint32_t *only) {
 	constexpr int T = ONLY ? CORR_THREADS_BIG : CORR_THREADS;  // threads of the workgroup
@@ -1047,8 +1045,7 @@ k_correct_fine(const int *ptiles, int n_ptiles, uint32_t *out_key, float *out_tx
 			float nt[3];
 #pragma unroll
 			for (int d = 0; d < 3; ++d) split_position(to[d], nn[d], nc[d], nt[d]);
-			out_key[jj] = blocked_index(g, nc[0], nc[1], nc[2]);
-			out_tx[jj] = nt[0]; out_ty[jj] = nt[1]; out_tz[jj] = nt[2];
+			pos_store(out, jj, blocked_index(g, nc[0], nc[1], nc[2]), nt[0], nt[1], nt[2]);
 		}
 #ifdef CORR_PROFILE
 		CORR_STAMP(2);  // thread 0's own particles
@@ -1128,7 +1125,7 @@ __global__ void k_source_seed(const uint32_t *cell, const uint32_t *src_of, cons
 	const float *vel = src_vel + 3 * src_of[i];
 	for (uint32_t j = 0; j < cnt; ++j) {
 		const size_t d = base + off[i] + j;
-		p.key[d] = b;
+		float tt[3];
 #pragma unroll
 		for (int a = 0; a < 3; ++a) {
 			// the generator is keyed on the particle's own slot d (unique over every entry of a call, so two entries that top up
@@ -1136,9 +1133,10 @@ __global__ void k_source_seed(const uint32_t *cell, const uint32_t *src_of, cons
 			// (a slab rank keys on the particle's id in the whole job, id_base + its index among this call's new particles)
 			const uint64_t r = mix64(seed + ((id_base + (uint64_t)(d - base)) * 3ull + (uint64_t)a + 1ull) * 0x9E3779B97F4A7C15ull + ((uint64_t)b << 40));
 			float t = (float)(r >> 40) * (1.0f / 16777216.0f);  // 24 random bits: [0, 1)
-			p.t[a][d] = t;
+			tt[a] = t;
 			p.v[a][d] = vel[a];
 		}
+		pos_store(p.pos, d, b, tt[0], tt[1], tt[2]);
 		particle_zero_c_set_id(p, d, (uint32_t)(id_base + (uint64_t)(d - base)));
 	}
 }
@@ -1570,41 +1568,39 @@ extern "C" int lfa_advect(lfa_sim *s, double dt) { return advect_collide(s, dt, 
 namespace {
 /// _detect_collisions as its own pass (lfa_collide): from = the position saved before the move, to = the current one.
 __global__ void __launch_bounds__(256)
-k_collide_only(size_t n, ParticleSoA p, const uint32_t *old_key, const float *ot0, const float *ot1, const float *ot2, GridDims g,
+k_collide_only(size_t n, ParticleSoA p, const PosRec *old, GridDims g,
                const uint8_t *solid, double skin) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const uint32_t key = p.key[i];
+	const PosRec me = pos_load(p.pos, i);
+	const uint32_t key = me.key;
 	if (key == 0xFFFFFFFFu) return;
+	const PosRec was = old ? pos_load(old, i) : me;
 	const int nn[3] = {g.nx, g.ny, g.nz};
 	int c[3], oc[3];
 	cell_of_key(g, key, c);
 	double from[3], to[3];
-	const float ot[3] = {ot0 ? ot0[i] : p.t[0][i], ot1 ? ot1[i] : p.t[1][i], ot2 ? ot2[i] : p.t[2][i]};
-	cell_of_key(g, old_key ? old_key[i] : key, oc);
+	cell_of_key(g, was.key, oc);
 #pragma unroll
 	for (int d = 0; d < 3; ++d) {
-		to[d] = (double)c[d] + (double)p.t[d][i];
-		from[d] = (double)oc[d] + (double)ot[d];
+		to[d] = (double)c[d] + (double)me.t[d];
+		from[d] = (double)oc[d] + (double)was.t[d];
 	}
 	collide(g, solid, from, to, skin);
 	int nc[3];
 	float nt[3];
 #pragma unroll
 	for (int d = 0; d < 3; ++d) split_position(to[d], nn[d], nc[d], nt[d]);
-	p.key[i] = blocked_index(g, nc[0], nc[1], nc[2]);
-#pragma unroll
-	for (int d = 0; d < 3; ++d) p.t[d][i] = nt[d];
+	pos_store(p.pos, i, blocked_index(g, nc[0], nc[1], nc[2]), nt[0], nt[1], nt[2]);
 }
 }  // namespace
 
-/// The positions (key, t) of before a split move go to the other buffer's key / t arrays (free between a binning and the G2P, and
+/// The position records of before a split move go to the other buffer's pos array (free between a binning and the G2P, and
 /// after the materialisation at the start of a step), where lfa_collide and a download in between (old_position) find them.
 static int save_old_positions(lfa_sim *s, size_t n) {
 	if (!n) return LFA_OK;
 	ParticleSoA &cur = s->pb[s->cur], &oth = s->pb[s->cur ^ 1];
-	LFA_HIP(s, hipMemcpyAsync(oth.key, cur.key, n * 4, hipMemcpyDeviceToDevice, s->stream));
-	for (int d = 0; d < 3; ++d) LFA_HIP(s, hipMemcpyAsync(oth.t[d], cur.t[d], n * 4, hipMemcpyDeviceToDevice, s->stream));
+	LFA_HIP(s, hipMemcpyAsync(oth.pos, cur.pos, n * sizeof(PosRec), hipMemcpyDeviceToDevice, s->stream));
 	return LFA_OK;
 }
 
@@ -1620,8 +1616,7 @@ extern "C" int lfa_collide(lfa_sim *s) {
 	ParticleSoA &cur = s->pb[s->cur], &oth = s->pb[s->cur ^ 1];
 	// nothing pending (an upload in between has replaced the particles): from = to, i.e. the skin push-out alone
 	hipLaunchKernelGGL(k_collide_only, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, cur,
-	                   pending ? (const uint32_t *)oth.key : (const uint32_t *)nullptr, pending ? (const float *)oth.t[0] : (const float *)nullptr,
-	                   pending ? (const float *)oth.t[1] : (const float *)nullptr, pending ? (const float *)oth.t[2] : (const float *)nullptr, s->g,
+	                   pending ? (const PosRec *)oth.pos : (const PosRec *)nullptr, s->g,
 	                   (const uint8_t *)s->solid, move_params(s, 0.0).skin);
 	LFA_LAUNCH_CHECK(s);
 	s->unknown_count_valid = false;
@@ -1654,8 +1649,8 @@ static int correct_build_index(lfa_sim *s, bool exchange = true) {
 	const int grid = n_index < 16384 ? (n_index > 0 ? n_index : 1) : 16384;
 	ParticleSoA &cur = s->pb[s->cur];
 	if (n) LFA_TRY(lfa_ev_record(s, LFA_EV_CORR_BEGIN));
-	hipLaunchKernelGGL(k_build_fine_index, dim3(grid), dim3(FIDX_THREADS), 0, s->stream, s->dist ? s->ptiles_all : s->ptiles, n_index, cur.key,
-	                   cur.t[0], cur.t[1], cur.t[2], s->tile_start, s->tile_count, s->fine_start, correction_scratch(s), s->pb[s->cur ^ 1].key);
+	hipLaunchKernelGGL(k_build_fine_index, dim3(grid), dim3(FIDX_THREADS), 0, s->stream, s->dist ? s->ptiles_all : s->ptiles, n_index,
+	                   (const PosRec *)cur.pos, s->tile_start, s->tile_count, s->fine_start, correction_scratch(s), s->bkey);
 	LFA_LAUNCH_CHECK(s);
 	return LFA_OK;
 }
@@ -1665,7 +1660,7 @@ static int correct_apply(lfa_sim *s, double dt, bool migrate = true, bool with_c
 	const size_t n = s->np_live;
 	MoveParams mpc = move_params(s, dt);
 	mpc.collide = with_collide ? 1 : 0;
-	ParticleSoA &cur = s->pb[s->cur], &oth = s->pb[s->cur ^ 1];
+	ParticleSoA &cur = s->pb[s->cur];
 	float4 *spos = correction_scratch(s);
 	if (n) {
 		// LDS-tiled pass; half tiles whose neighbourhood exceeds the LDS capacity are flagged and redone, first by the same kernel
@@ -1685,23 +1680,23 @@ static int correct_apply(lfa_sim *s, double dt, bool migrate = true, bool with_c
 			const int work = CORR_PARTS * s->n_ptiles, g2 = work < 65536 ? (work > 0 ? work : 1) : 65536;
 			// every neighbour position comes from the records of the index built above (the OLD positions), so the new ones are
 			// written in place; the fallback pass below takes its particles' old state from the records and the copy of the keys
-			// the index kernel has left in the other buffer
+			// the index kernel has left in bkey
 			LFA_TRY(lfa_ev_record(s, LFA_EV_CORR_INDEXED));
-			hipLaunchKernelGGL((k_correct_fine<FINE_CAP, false>), dim3(g2), dim3(CORR_THREADS), 0, s->stream, s->ptiles, s->n_ptiles, cur.key,
-			                   cur.t[0], cur.t[1], cur.t[2], s->g, s->solid, s->tile_count, s->fine_start, (const float4 *)spos, mpc, ovf,
+			hipLaunchKernelGGL((k_correct_fine<FINE_CAP, false>), dim3(g2), dim3(CORR_THREADS), 0, s->stream, s->ptiles, s->n_ptiles, cur.pos,
+			                   s->g, s->solid, s->tile_count, s->fine_start, (const float4 *)spos, mpc, ovf,
 			                   (const uint8_t *)s->tile_clear, (const uint32_t *)nullptr);
 			LFA_LAUNCH_CHECK(s);
 			LFA_TRY(lfa_ev_record(s, LFA_EV_CORR_TILED));
 			// (a workgroup per CU and a few more: they return at once unless something is flagged)
 			hipLaunchKernelGGL((k_correct_fine<FINE_CAP_BIG, true>), dim3(std::min(CORR_BIG_SLICES * g2, 2048)), dim3(CORR_THREADS_BIG), 0, s->stream, s->ptiles,
-			                   s->n_ptiles, cur.key, cur.t[0], cur.t[1], cur.t[2], s->g, s->solid, s->tile_count, s->fine_start,
+			                   s->n_ptiles, cur.pos, s->g, s->solid, s->tile_count, s->fine_start,
 			                   (const float4 *)spos, mpc, ovf2, (const uint8_t *)s->tile_clear, (const uint32_t *)ovf);
 			LFA_LAUNCH_CHECK(s);
 		}
 		const uint32_t *fallback = ovf2;
-		hipLaunchKernelGGL(k_correct_collide, dim3((unsigned)std::min<size_t>((n + 255) / 256, 16384)), dim3(256), 0, s->stream, n, cur, cur.key, cur.t[0],
-		                   cur.t[1], cur.t[2], s->g, s->solid, s->tile_count, s->fine_start, (const float4 *)spos, mpc,
-		                   fallback, (const int *)s->tile_pslot, s->p_off, (const uint32_t *)oth.key);
+		hipLaunchKernelGGL(k_correct_collide, dim3((unsigned)std::min<size_t>((n + 255) / 256, 16384)), dim3(256), 0, s->stream, n, cur, cur.pos,
+		                   s->g, s->solid, s->tile_count, s->fine_start, (const float4 *)spos, mpc,
+		                   fallback, (const int *)s->tile_pslot, s->p_off, (const uint32_t *)s->bkey);
 		LFA_LAUNCH_CHECK(s);
 	}
 	if (migrate) LFA_TRY(lfa_dist_migrate(s));
@@ -1729,9 +1724,8 @@ extern "C" int lfa_correct(lfa_sim *s, double dt) {
 	s->move_pending = false;
 	if (!s->np_live && !s->dist) return LFA_OK;
 	LFA_TRY(correct_build_index(s));  // (slabs: with the ghost exchange - every rank takes part)
-	// the positions of before: the keys are copied by correct_apply itself (other buffer), the fractions here
-	ParticleSoA &cur = s->pb[s->cur], &oth = s->pb[s->cur ^ 1];
-	for (int d = 0; d < 3 && s->np_live; ++d) LFA_HIP(s, hipMemcpyAsync(oth.t[d], cur.t[d], s->np_live * 4, hipMemcpyDeviceToDevice, s->stream));
+	// the positions of before: the records go to the other buffer, whole
+	LFA_TRY(save_old_positions(s, s->np_live));
 	LFA_TRY(correct_apply(s, dt, false, false));  // (no migration yet: lfa_collide hands the particles over)
 	s->move_pending = true;
 	return LFA_OK;
@@ -1785,16 +1779,16 @@ namespace {
 /// (key, t) of before the correction: the keys from their copy, the fractions from the cell-ordered records (record k
 /// belongs to particle spos[k].w) - both are inputs the correction does not write.
 __global__ void __launch_bounds__(256)
-k_correct_undo(size_t n, const float4 *spos, const uint32_t *old_key, uint32_t *key, float *t0, float *t1, float *t2) {
+k_correct_undo(size_t n, const float4 *spos, const uint32_t *old_key, PosRec *pos) {
 	const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (k >= n) return;
 	const float4 rec = spos[k];
 	const uint32_t i = __float_as_uint(rec.w);
 	// (the records of the fine index keep cell bits in the two top bits of the fractions: fine_record)
-	t0[i] = __uint_as_float(__float_as_uint(rec.x) & 0x3FFFFFFFu);
-	t1[i] = __uint_as_float(__float_as_uint(rec.y) & 0x3FFFFFFFu);
-	t2[i] = __uint_as_float(__float_as_uint(rec.z) & 0x3FFFFFFFu);
-	key[k] = old_key[k];
+	pos[i].t[0] = __uint_as_float(__float_as_uint(rec.x) & 0x3FFFFFFFu);
+	pos[i].t[1] = __uint_as_float(__float_as_uint(rec.y) & 0x3FFFFFFFu);
+	pos[i].t[2] = __uint_as_float(__float_as_uint(rec.z) & 0x3FFFFFFFu);
+	pos[k].key = old_key[k];
 }
 }  // namespace
 
@@ -1811,9 +1805,9 @@ extern "C" int lfa_correct_collide_undo(lfa_sim *s) {
 	s->corr_begun = false;
 	const size_t n = s->np_live;
 	if (!n) return LFA_OK;
-	ParticleSoA &cur = s->pb[s->cur], &oth = s->pb[s->cur ^ 1];
+	ParticleSoA &cur = s->pb[s->cur];
 	hipLaunchKernelGGL(k_correct_undo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, (const float4 *)correction_scratch(s),
-	                   (const uint32_t *)oth.key, cur.key, cur.t[0], cur.t[1], cur.t[2]);
+	                   (const uint32_t *)s->bkey, cur.pos);
 	LFA_LAUNCH_CHECK(s);
 	return LFA_OK;
 }

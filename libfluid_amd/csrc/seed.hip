@@ -106,8 +106,7 @@ __device__ inline void born_particle(const ParticleSoA &p, size_t d, const GridD
 	float tx, ty;
 	cell_and_fraction(x[0], ip.off[0], ip.h, g.nx, cx, tx);
 	cell_and_fraction(x[1], ip.off[1], ip.h, g.ny, cy, ty);
-	p.key[d] = blocked_index(g, cx, cy, cz);
-	p.t[0][d] = tx; p.t[1][d] = ty; p.t[2][d] = tz;
+	pos_store(p.pos, d, blocked_index(g, cx, cy, cz), tx, ty, tz);
 	p.v[0][d] = v0; p.v[1][d] = v1; p.v[2][d] = v2;
 	particle_zero_c_set_id(p, d, id);
 	if (pos_out) {
