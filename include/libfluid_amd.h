@@ -458,7 +458,10 @@ int lfa_correct_collide(lfa_sim *s, double dt);
  * the particles and keep the positions of before on the device; a download in between reports them as old_position;
  * lfa_collide runs _detect_collisions (:612-683) from there to the current positions. After an upload in between lfa_collide
  * starts from the uploaded positions (from = to: the skin push-out alone). Slab decompositions: the particles change rank in
- * lfa_collide, once they have their final positions (a collective: every rank calls it). */
+ * lfa_collide, once they have their final positions (a collective: every rank calls it).
+ * Every stage that hands particles over (lfa_advect_collide, lfa_collide, lfa_correct_collide, lfa_time_step) hands them to the
+ * adjacent rank: a particle that ends in a tile layer the adjacent rank does not own makes its rank return LFA_E_UNSUPPORTED
+ * before anything is handed over and closes the transport (the peers' next exchange fails); the job's handles are unusable then. */
 int lfa_advect(lfa_sim *s, double dt);
 int lfa_correct(lfa_sim *s, double dt);
 int lfa_collide(lfa_sim *s);

@@ -133,6 +133,7 @@ struct lfa_sim {
 	// [slab_lo, slab_hi) and mirrors one ghost tile layer on each side. dist == nullptr: single domain.
 	struct lfa_dist *dist = nullptr;
 	int slab_lo = 0, slab_hi = 0;           // owned tile layers (z)
+	int slab_reach_lo = 0, slab_reach_hi = 0;  // the tile layers of this rank and its two neighbours: where a migration can deliver
 	int slab_align = 0;                     // every interior slab bound is a multiple of 2^slab_align tile layers
 	int *ptiles_all = nullptr;              // ghost-lo | owned | ghost-hi particle tiles, ascending tile id
 	int p_off = 0, n_ptiles_all = 0;        // ptiles == ptiles_all + p_off

@@ -352,7 +352,7 @@ namespace {
 __global__ void __launch_bounds__(256)
 k_pack_leavers(size_t n, ParticleSoA p, int tiles_per_layer, int slab_lo, int slab_hi, uint32_t *counters, uint32_t *buf_lo,
                uint32_t *buf_hi, int count_only, const float *c_home, size_t c_home_stride, ParticleSoA pvc, const uint32_t *from,
-               int c_deferred) {
+               int c_deferred, int reach_lo, int reach_hi) {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	int dest = -1;
 	uint32_t key = 0xFFFFFFFFu;
@@ -361,6 +361,9 @@ k_pack_leavers(size_t n, ParticleSoA p, int tiles_per_layer, int slab_lo, int sl
 		if (key != 0xFFFFFFFFu) {
 			const int tz = (int)(key >> 9) / tiles_per_layer;
 			dest = tz < slab_lo ? 0 : (tz >= slab_hi ? 1 : -1);
+			// (counting pass: a leaver whose layer is not the adjacent rank's - [reach_lo, slab_lo) below, [slab_hi, reach_hi) above -
+			// would be handed to a rank that does not own it; counters[4] tells the host, which refuses the move)
+			if (count_only && (tz < reach_lo || tz >= reach_hi)) atomicAdd(&counters[4], 1u);
 		}
 	}
 	const int lane = threadIdx.x & 63;
@@ -419,7 +422,13 @@ __global__ void __launch_bounds__(256) k_unpack_arrivals(size_t n, const uint32_
 int lfa_particles_reserve(lfa_sim *s, size_t n_keep, size_t n_total);  // core.hip
 
 /// After a stage that moves particles (advect+collide, correct+collide): hand the particles that left the slab to the
-/// neighbour ranks and take theirs. Moves of more than one slab per step are not handled (CFL bounds a step to 3 cells).
+/// neighbour ranks and take theirs. A particle goes to the ADJACENT rank only. A move that ends in a layer the adjacent rank does
+/// not own - more than one slab in one stage: a caller's dt beyond the CFL bound of 3 cells, or slabs of one ragged cell layer -
+/// is refused: the counting pass counts such leavers, and a rank that has one returns LFA_E_UNSUPPORTED before any particle record
+/// is packed or sent (only the four leave counts have crossed) and breaks the transport, so that its peers' next call fails at once
+/// and does not wait for this rank. The handles of the job are unusable from then on: the other ranks have given up in the
+/// middle of a collective stage, and nothing says which particles they hold. (Forwarded unnoticed, such a particle was counted into
+/// a tile of no list of its new rank and took part in neither transfer of the step.)
 /// `vc_dead`: the caller is about to run the G2P, which overwrites v (and, APIC, C) of every live particle without reading them
 /// (PIC, APIC; FLIP blends with the old velocity): a deferred binning then need not be completed for the leavers' sake - the
 /// records travel with whatever v / C the current buffer holds.
@@ -429,21 +438,29 @@ int lfa_dist_migrate(lfa_sim *s, bool vc_dead) {
 	// 0.12 ms per migration at C3 -: the pack kernel reads v, C where they are, the arrivals' go behind the other buffer's records)
 	(void)vc_dead;
 	const size_t n = s->binned ? s->np_live : s->np;
-	uint32_t *cnt = (uint32_t *)(s->dist_red + LFA_DR_MIGRATE_COUNTS);  // [0,1] leaving lo/hi, [2,3] arriving from lo/hi
-	LFA_HIP(s, hipMemsetAsync(cnt, 0, 16, s->stream));
+	uint32_t *cnt = (uint32_t *)(s->dist_red + LFA_DR_MIGRATE_COUNTS);  // [0,1] leaving lo/hi, [2,3] arriving from lo/hi, [4] too far
+	LFA_HIP(s, hipMemsetAsync(cnt, 0, 20, s->stream));
 	const int tpl = s->g.ntx * s->g.nty;
 	const dim3 grid((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1));
 	ParticleSoA &p = s->pb[s->cur];
 	hipLaunchKernelGGL(k_pack_leavers, grid, dim3(256), 0, s->stream, n, p, tpl, s->slab_lo, s->slab_hi, cnt, (uint32_t *)nullptr,
-	                   (uint32_t *)nullptr, 1, (const float *)nullptr, (size_t)0, p, (const uint32_t *)nullptr, 0);
+	                   (uint32_t *)nullptr, 1, (const float *)nullptr, (size_t)0, p, (const uint32_t *)nullptr, 0, s->slab_reach_lo,
+	                   s->slab_reach_hi);
 	LFA_LAUNCH_CHECK(s);
 	// how many arrive: the neighbours' leave counts
 	LFA_TRY(s->dist->exchange(s, lfa_has_lo(s) ? cnt + 0 : nullptr, lfa_has_lo(s) ? 4 : 0, lfa_has_lo(s) ? cnt + 2 : nullptr,
 	                          lfa_has_lo(s) ? 4 : 0, lfa_has_hi(s) ? cnt + 1 : nullptr, lfa_has_hi(s) ? 4 : 0,
 	                          lfa_has_hi(s) ? cnt + 3 : nullptr, lfa_has_hi(s) ? 4 : 0));
-	uint32_t h[4];
-	LFA_HIP(s, hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, s->stream));
+	uint32_t h[5];
+	LFA_HIP(s, hipMemcpyAsync(h, cnt, 20, hipMemcpyDeviceToHost, s->stream));
 	LFA_HIP(s, hipStreamSynchronize(s->stream));
+	if (h[4]) {
+		s->dist->give_up();
+		return lfa_fail(s, LFA_E_UNSUPPORTED,
+		                "slab migration: %u particles of rank %d moved beyond the adjacent slab in one stage (own tile layers [%d, %d), a "
+		                "neighbour slab is %d and %d layers thick); the transport is closed and the handles of this job are unusable",
+		                h[4], s->dist->rank, s->slab_lo, s->slab_hi, s->slab_lo - s->slab_reach_lo, s->slab_reach_hi - s->slab_hi);
+	}
 	if (!lfa_has_lo(s)) h[0] = h[2] = 0;  // nothing can leave through a domain wall (positions are clamped into the grid)
 	if (!lfa_has_hi(s)) h[1] = h[3] = 0;
 	// (no early-out when nothing crosses this rank's faces: every rank issues the same sequence of transport calls)
@@ -461,7 +478,7 @@ int lfa_dist_migrate(lfa_sim *s, bool vc_dead) {
 	float *chome = s->c_home_valid ? s->c_home : nullptr;
 	hipLaunchKernelGGL(k_pack_leavers, grid, dim3(256), 0, s->stream, n, q, tpl, s->slab_lo, s->slab_hi, cnt,
 	                   (uint32_t *)s->xbuf[0], (uint32_t *)s->xbuf[1], 0, (const float *)chome, s->c_home_cap, pend ? qo : q,
-	                   (const uint32_t *)from, s->vc_with_c ? 1 : 0);
+	                   (const uint32_t *)from, s->vc_with_c ? 1 : 0, s->slab_reach_lo, s->slab_reach_hi);
 	LFA_LAUNCH_CHECK(s);
 	LFA_TRY(s->dist->exchange(s, s->xbuf[0], (size_t)h[0] * 68, s->xbuf[2], (size_t)h[2] * 68, s->xbuf[1], (size_t)h[1] * 68,
 	                          s->xbuf[3], (size_t)h[3] * 68));
@@ -999,6 +1016,8 @@ int attach(lfa_sim *s, lfa_dist *d, const int32_t *bounds) {
 	for (int r = 1; r < d->nranks; ++r) s->slab_align = std::min(s->slab_align, __builtin_ctz((unsigned)bounds[r]));
 	s->slab_lo = lo;
 	s->slab_hi = hi;
+	s->slab_reach_lo = bounds[d->rank > 0 ? d->rank - 1 : 0];
+	s->slab_reach_hi = bounds[d->rank + 1 < d->nranks ? d->rank + 2 : d->nranks];
 	s->binned = false;
 	s->sources_valid = false;  // the seeding entries are the ones of this rank's own tile layers ...
 	s->sources_built.clear();  // ... so entries flattened for another range (the whole domain, earlier bounds) are not "the same list"

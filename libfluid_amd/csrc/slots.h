@@ -90,7 +90,7 @@ enum {
 	LFA_DR_SIGMA = 3,           // solver: sigma, + parity [3, 5)
 	LFA_DR_SOURCE_TOTALS = 16,  // particles.hip, lfa_update_sources: one slot per rank. Beyond 16 ranks it runs into the two claims
 	                            // below; each of the three is written, reduced and read back inside one call
-	LFA_DR_MIGRATE_COUNTS = 32,  // dist.hip, lfa_dist_migrate: four uint32 - leaving lo / hi, arriving from lo / hi
+	LFA_DR_MIGRATE_COUNTS = 32,  // dist.hip, lfa_dist_migrate: five uint32 - leaving lo / hi, arriving from lo / hi, beyond reach
 	LFA_DR_GHOST_TOTALS = 40,   // dist.hip, ghost particles: two uint32 - arriving from below / above
 	LFA_DR_GATHER = 64,         // two gather buffers (parity), each [max | sum | sum2 per rank | given up]: lfa_dist_gather_buf
 	LFA_DR_GATHER_LEN = 3 * LFA_DR_MAX_RANKS + 1,

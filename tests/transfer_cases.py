@@ -151,6 +151,38 @@ def lone_hats(h=1.0, unscaled=False, seed=404):
     return size, parts, solid, meta
 
 
+def zmirror(cloud):
+    """A cloud reflected z -> nz - z (in cells; world z -> 2 off_z + nz h - z): what went down across a cell face goes up. Velocities and C
+    stay as drawn (the cloud need not be the mirror image of a flow, only put its weights on the mirrored faces). The hats' face
+    cells are reflected with the staggering: the w face of cell z lies at z + 1, so it becomes the w face of cell nz - 2 - z; a u or
+    v face at z + 1/2 becomes the one of cell nz - 1 - z. Metadata that names tiles is dropped (nz need not be a whole number of
+    tiles); meta["zmirror"] = True."""
+    size, parts, solid, meta = cloud
+    assert solid is None
+    nz, h, off = size[2], meta["h"], meta["off"]
+    parts = parts.copy()
+    parts["pos"][:, 2] = (2.0 * off[2] + nz * h) - parts["pos"][:, 2]
+    parts["old_pos"] = parts["pos"]
+    meta = {k: v for k, v in meta.items() if k not in ("interior_tile", "ragged_tile", "lonely_tile", "per_tile")}
+    if "hats" in meta:
+        meta["hats"] = [dict(hat, cell=(hat["cell"][0], hat["cell"][1], nz - (2 if hat["comp"] == 2 else 1) - hat["cell"][2]))
+                        for hat in meta["hats"]]
+    meta["zmirror"] = True
+    assert len(np.unique(parts["pos"], axis=0)) == len(parts)
+    return size, parts, solid, meta
+
+
+def above(cloud, z):
+    """The particles of a cloud in the cell layers >= z, the hats' indices following them."""
+    size, parts, solid, meta = cloud
+    keep = np.floor((parts["pos"][:, 2] - meta["off"][2]) / meta["h"]) >= z
+    new = np.cumsum(keep) - 1
+    meta = dict(meta)
+    if "hats" in meta:
+        meta["hats"] = [dict(hat, index=int(new[hat["index"]])) for hat in meta["hats"] if keep[hat["index"]]]
+    return size, parts[keep].copy(), solid, meta
+
+
 def fast(vmax, seed=505, h=1.0):
     """The (9, 8, 7) contrast cloud with velocity components uniform in [-vmax, vmax] and C entries uniform in [-vmax, vmax] / (3 h):
     the affine term c . (face - p) of a face one cell away adds up to the same magnitude."""
@@ -237,6 +269,14 @@ CASES = {
     "thin_2_9_17": lambda: thin((2, 9, 17)),
     "thin_17_2_9": lambda: thin((17, 2, 9)),
     "thin_5_5_5": lambda: thin((5, 5, 5)),
+    # (tests/slab_face_cases.py: the hats of the originals that cross z = 8 all cross it downwards; these cross it upwards. A
+    # mirrored `lattice` would not: a fraction of 0 or 1/2 never reaches the cell above, mirrored or not)
+    "lone_hats_zmirror": lambda: zmirror(lone_hats(1.0, False)),
+    "lone_hats_h17_zmirror": lambda: zmirror(lone_hats(1.7, False)),
+    "lone_hats_h17_unscaled_zmirror": lambda: zmirror(lone_hats(1.7, True)),
+    # nothing below (mirrored: above) z = 8: the hats across that face end in tiles of a layer that holds no particle at all
+    "lone_hats_above_z8": lambda: above(lone_hats(1.0, False), 8),
+    "lone_hats_above_z8_zmirror": lambda: zmirror(above(lone_hats(1.0, False), 8)),
 }
 
 
