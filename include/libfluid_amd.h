@@ -235,8 +235,10 @@ int lfa_sample_velocity_time(lfa_sim *s, double *ms);
  * detect_collisions and PIC transfer bit for bit. Two deliberate differences, invisible on finite inputs: the march of a bounce
  * takes at most nx + ny + nz + 3 face crossings, and a tracer whose moved position is not finite in every coordinate (a NaN
  * velocity) is FROZEN: it keeps its position, is counted, and still takes a new velocity in 3.
- * Single domain only: lfa_tracers_add on a handle with a slab decomposition, and lfa_dist_init_* on a handle that holds tracers,
- * return LFA_E_UNSUPPORTED before anything is touched (tracers that migrate between ranks are the follow-up).
+ * The eight calls below are the single domain's. On a handle with a slab decomposition lfa_tracers_add, _advect_collide, _transfer
+ * and _step return LFA_E_UNSUPPORTED before anything is touched (counts and arrays included) - the _collective calls further down
+ * take their place -, and lfa_dist_init_* refuses a handle that holds tracers; _count, _clear, _time and _download are local and work
+ * there (the rank's own tracers, in storage order).
  *   lfa_tracers_add            : appends n tracers in order; a tracer's index is its rank over all adds since the last clear. xyz
  *                                double[3 n] (host), velocity double[3 n] or NULL: zeros. The total stays below 2^32. A non-finite
  *                                position is LFA_E_INVALID, the message names the first bad index; checked on the host before
@@ -261,6 +263,58 @@ int lfa_tracers_transfer(lfa_sim *s);
 int lfa_tracers_step(lfa_sim *s, double dt, uint64_t counts[2]);
 int lfa_tracers_download(lfa_sim *s, double *xyz, double *velocity, uint8_t *types, uint64_t n);
 int lfa_tracers_time(lfa_sim *s, double *ms);
+/* -- tracers on a slab decomposition ----------------------------------------------------------------------------------------------
+ * COLLECTIVE: every rank of the job makes each of these calls, a rank that holds no tracer too. Between calls the job holds a
+ * PARTITION of the single domain's tracers: gathered by id, the ranks' positions, velocities and type bytes after k collective steps
+ * are the bytes lfa_tracers_download gives on a single-domain handle after k plain steps on the ranks' grids stitched by owned
+ * z-range - the move and the collision handling read the solid cells alone, which every rank holds whole, and the transfer is
+ * lfa_sample_velocity_collective's: the ghost refresh, then sample_value under the owners' tile rules.
+ *   id       : a tracer's index over all adds of the JOB since the last clear, a uint32_t. On a slab handle it is stored beside the
+ *              record and travels with it; a single-domain handle stores none (there the id is the storage index).
+ *   owner    : the rank whose tile layers hold cz >> 3, cz = floor((z - grid_offset_z) / cell_size) with lfa_sample_velocity's fp64
+ *              division, clamped to [0, nz - 1] on the double before any cast. x and y play no part, so a tracer added outside the
+ *              grid has an owner too, and its first move clamps it in as on a single domain.
+ *   far moves: a tracer's first velocity is the caller's and the move is only clamped to the box, so one step can carry a tracer
+ *              across several slabs. Unlike the particle migration, which refuses such a move (and with it the job), the tracers are
+ *              FORWARDED hop by hop: after the move every rank finds the lowest and the highest destination layer of the tracers
+ *              it no longer owns, maps them to a hop distance through the layer bounds given at init, and ONE max all-reduce makes
+ *              it the job's round count R. R rounds follow, each a count exchange and a payload exchange with z-1 / z+1 (56 bytes per
+ *              record: six doubles, id and type); a round sends every record a rank holds and does not own, arrivals of the round
+ *              before included, down or up by the owner's side. R == 0 - nothing crosses anywhere - costs the all-reduce alone.
+ *   placement: deterministic, no atomic decides a position. After a call a rank's arrays are compact: the stayers first, in their
+ *              previous order, then the arrivals from below, then those from above, each in the sender's order. Two runs of a job
+ *              write the same bytes in the same order on every rank. Arrivals beyond the capacity grow the arrays (everything new
+ *              is allocated before anything old is released); a rank that cannot (LFA_E_OOM) closes the transport, so that its
+ *              peers' calls fail at once instead of waiting.
+ * Order inside every call, as in lfa_sample_velocity_collective: 1. what the handle's state decides and is the same on every rank
+ * - dt finite, cell_size set, for the transfer: binned by a collective lfa_hash_particles -, otherwise LFA_E_INVALID on every rank
+ * and no message is sent; 2. the transport calls; 3. this rank's own work.
+ * On a SINGLE DOMAIN each call is local, sends no message and equals the plain call it replaces, so one host code serves 1 and N
+ * ranks.
+ *   lfa_tracers_add_collective            : replaces lfa_tracers_add. Every rank passes the SAME list; the rank keeps the tracers it
+ *                                           owns, in list order, with id = first_id + index in the list. first_id advances by n on
+ *                                           every rank, also on one that keeps nothing. counts (or NULL): [0] kept here, [1] the
+ *                                           first_id of this call. The host checks of lfa_tracers_add run on every rank alike before
+ *                                           anything is queued (non-finite position; 2^32 tracers or more in the JOB). No message.
+ *   lfa_tracers_advect_collide_collective : replaces lfa_tracers_advect_collide: its kernel on the resident tracers, then the
+ *                                           migration above. counts (or NULL): [0] stopped, [1] frozen - both of the tracers
+ *                                           resident before the move; a frozen tracer keeps its position and so its rank -,
+ *                                           [2] records handed down, [3] handed up, [4] records received (a forwarded record counts
+ *                                           on every rank it passes: over the job, sum of [2] + [3] == sum of [4]), [5] the rounds R.
+ *   lfa_tracers_transfer_collective       : replaces lfa_tracers_transfer: the ghost refresh of lfa_sample_velocity_collective (two
+ *                                           transport calls, also on a rank with no tracers), then the transfer of the resident ones.
+ *   lfa_tracers_step_collective           : replaces lfa_tracers_step: the two calls above in sequence, with the state checks of both
+ *                                           in front, and the same bits. NOT one kernel on slabs - the migration sits between the
+ *                                           stages (on a single domain it is lfa_tracers_step's fused kernel).
+ *   lfa_tracers_download_ids              : local. lfa_tracers_download with ids uint32[n] (or NULL) in front: the rank's rows in
+ *                                           storage order and their ids; on a single domain 0 .. n - 1. n = lfa_tracers_count.
+ * lfa_tracers_clear on a slab handle also resets first_id, so EVERY rank has to call it; lfa_tracers_time then covers the move and
+ * the rank's share of the migration (or the transfer kernel). */
+int lfa_tracers_add_collective(lfa_sim *s, const double *xyz, const double *velocity, uint64_t n, uint64_t counts[2]);
+int lfa_tracers_advect_collide_collective(lfa_sim *s, double dt, uint64_t counts[6]);
+int lfa_tracers_transfer_collective(lfa_sim *s);
+int lfa_tracers_step_collective(lfa_sim *s, double dt, uint64_t counts[6]);
+int lfa_tracers_download_ids(lfa_sim *s, uint32_t *ids, double *xyz, double *velocity, uint8_t *types, uint64_t n);
 /* Synthetic dam-break block [lo,hi) in cells, 8 jittered particles per cell, generated on the device; bit-identical
  * to libfluid_amd/scenes.py:seed_block. */
 int lfa_seed_block(lfa_sim *s, const int64_t lo[3], const int64_t hi[3], uint64_t seed);

@@ -106,6 +106,11 @@ SIGNATURES = {
     "lfa_tracers_step": (_int, [_vp, _dbl, C.POINTER(_u64 * 2)]),
     "lfa_tracers_download": (_int, [_vp, _vp, _vp, _vp, _u64]),
     "lfa_tracers_time": (_int, [_vp, C.POINTER(_dbl)]),
+    "lfa_tracers_add_collective": (_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64 * 2)]),
+    "lfa_tracers_advect_collide_collective": (_int, [_vp, _dbl, C.POINTER(_u64 * 6)]),
+    "lfa_tracers_transfer_collective": (_int, [_vp]),
+    "lfa_tracers_step_collective": (_int, [_vp, _dbl, C.POINTER(_u64 * 6)]),
+    "lfa_tracers_download_ids": (_int, [_vp, _vp, _vp, _vp, _vp, _u64]),
     "lfa_seed_block": (_int, [_vp, _vp, _vp, _u64]),
     "lfa_seed_box": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
     "lfa_seed_sphere": (_int, [_vp, _vp, _dbl, _vp, _u64, C.POINTER(_u64), _int, C.POINTER(_u64), _vp, _u64]),
@@ -735,6 +740,46 @@ class Sim:
         typ = np.empty(n, dtype=np.uint8) if types else None
         self._chk(self.lib.lfa_tracers_download(self.h, _ptr(pos), _ptr(vel), None if typ is None else _ptr(typ), n))
         return (pos, vel, typ) if types else (pos, vel)
+
+    # -- tracers on a slab decomposition: COLLECTIVE, every rank makes each call; on a single domain they equal the plain calls ----
+    def add_tracers_collective(self, points, velocity=None):
+        """(kept, first_id): add_tracers() on a slab decomposition. Every rank passes the SAME list and keeps the tracers whose cell
+        layer it owns, in list order, with id = first_id + index in the list (lfa_tracers_add_collective)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        vel = None if velocity is None else np.ascontiguousarray(velocity, dtype=np.float64).reshape(-1, 3)
+        if vel is not None and vel.shape != pts.shape:
+            raise ValueError("velocity must have the shape of points")
+        counts = (_u64 * 2)()
+        self._chk(self.lib.lfa_tracers_add_collective(self.h, _ptr(pts), None if vel is None else _ptr(vel), pts.shape[0], C.byref(counts)))
+        return int(counts[0]), int(counts[1])
+
+    def tracers_advect_collide_collective(self, dt):
+        """(stopped, frozen, handed down, handed up, received, rounds): tracers_advect_collide(), then the tracers that left this
+        rank's tile layers go to their owners, hop by hop (lfa_tracers_advect_collide_collective)."""
+        counts = (_u64 * 6)()
+        self._chk(self.lib.lfa_tracers_advect_collide_collective(self.h, float(dt), C.byref(counts)))
+        return tuple(int(c) for c in counts)
+
+    def tracers_transfer_collective(self):
+        """tracers_transfer() behind the ghost refresh of sample_velocity_collective() (lfa_tracers_transfer_collective)."""
+        self._chk(self.lib.lfa_tracers_transfer_collective(self.h))
+
+    def tracers_step_collective(self, dt):
+        """The six counts of tracers_advect_collide_collective(): that call, then tracers_transfer_collective(), the same bits
+        (lfa_tracers_step_collective)."""
+        counts = (_u64 * 6)()
+        self._chk(self.lib.lfa_tracers_step_collective(self.h, float(dt), C.byref(counts)))
+        return tuple(int(c) for c in counts)
+
+    def tracers_with_ids(self, types=False):
+        """ids uint32[n], pos float64[n, 3], vel float64[n, 3][, types uint8[n]]: this rank's tracers in storage order with their
+        job-wide ids; 0 .. n - 1 on a single domain (lfa_tracers_download_ids)."""
+        n = self.num_tracers()
+        ids = np.empty(n, dtype=np.uint32)
+        pos, vel = np.empty((n, 3), dtype=np.float64), np.empty((n, 3), dtype=np.float64)
+        typ = np.empty(n, dtype=np.uint8) if types else None
+        self._chk(self.lib.lfa_tracers_download_ids(self.h, _ptr(ids), _ptr(pos), _ptr(vel), None if typ is None else _ptr(typ), n))
+        return (ids, pos, vel, typ) if types else (ids, pos, vel)
 
     def tracers_ms(self):
         """Device milliseconds of the last tracer kernel (lfa_tracers_time)."""

@@ -134,6 +134,7 @@ struct lfa_sim {
 	struct lfa_dist *dist = nullptr;
 	int slab_lo = 0, slab_hi = 0;           // owned tile layers (z)
 	int slab_reach_lo = 0, slab_reach_hi = 0;  // the tile layers of this rank and its two neighbours: where a migration can deliver
+	std::vector<int32_t> slab_bounds;       // the layer bounds of every rank as given at init (tracers.hip: hops to a far owner)
 	int slab_align = 0;                     // every interior slab bound is a multiple of 2^slab_align tile layers
 	int *ptiles_all = nullptr;              // ghost-lo | owned | ghost-hi particle tiles, ascending tile id
 	int p_off = 0, n_ptiles_all = 0;        // ptiles == ptiles_all + p_off
@@ -304,11 +305,18 @@ struct lfa_sim {
 	// tracers (tracers.hip): massless markers that move as PIC particles do and that no grid stage sees. One block from the pool: fp64
 	// x, y, z, vx, vy, vz [cap] each | the two count words of a step | the type bytes [cap]; nothing is allocated before the first
 	// lfa_tracers_add. The events sit around the last tracer kernel.
+	// Slabs (the collective calls): the block of a handle with a transport carries the job-wide ids uint32[cap] behind the type bytes
+	// (a single-domain block has none: there a tracer's id is its index); `n` is what THIS rank holds, first_id the number of tracers
+	// the job has added since the last clear - the same on every rank. `alt` is the second block of the migration's compaction: the
+	// stayers move to its front, the blocks change places.
 	struct Tracers {
 		void *base = nullptr;
 		size_t n = 0, cap = 0;
 		hipEvent_t ev[2] = {nullptr, nullptr};
 		bool timed = false;
+		void *alt = nullptr;
+		size_t alt_cap = 0;
+		uint64_t first_id = 0;
 	} tracers;
 
 	// timing

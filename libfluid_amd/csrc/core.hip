@@ -362,7 +362,7 @@ extern "C" void lfa_destroy(lfa_sim *s) {
 	                s->cell_count, s->stage, s->acc, s->abits, s->vp, s->vr, s->vz, s->vs, s->vpre, s->vq, s->vs2, s->c_as, s->nbr_table,
 	                s->partials, s->frame_part, s->pcg_state, s->pcg_hist, s->level_tiles, s->io_buf, s->raw_scan, s->c_diag, s->c_w[0],
 	                s->c_w[1], s->c_w[2], s->c_unk, s->c_pre, s->c_r, s->c_x, s->c_r2, s->c_x2, s->a2inv, s->slot_l1,
-	                s->l1_tiles, s->l1_l2, s->tracers.base};
+	                s->l1_tiles, s->l1_l2, s->tracers.base, s->tracers.alt};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (s->dist) delete s->dist;

@@ -991,11 +991,11 @@ struct ShmDist : lfa_dist {
 	}
 };
 
-/// Tracers live on a single domain (tracers.hip; migrating them between ranks is the follow-up): a handle that holds some takes no
+/// Tracers are owned by cell layer (tracers.hip) and a new decomposition has other owners: a handle that holds some takes no
 /// transport, and nothing of it is touched.
 static int refuse_with_tracers(lfa_sim *s, const char *who) {
 	if (s->tracers.n == 0) return LFA_OK;
-	return lfa_fail(s, LFA_E_UNSUPPORTED, "%s: the handle holds %zu tracers, which do not migrate between slabs yet (lfa_tracers_clear first)", who,
+	return lfa_fail(s, LFA_E_UNSUPPORTED, "%s: the handle holds %zu tracers, which a new decomposition would leave with the wrong rank (lfa_tracers_clear first, lfa_tracers_add_collective after)", who,
 	                s->tracers.n);
 }
 
@@ -1018,6 +1018,14 @@ int attach(lfa_sim *s, lfa_dist *d, const int32_t *bounds) {
 	s->slab_hi = hi;
 	s->slab_reach_lo = bounds[d->rank > 0 ? d->rank - 1 : 0];
 	s->slab_reach_hi = bounds[d->rank + 1 < d->nranks ? d->rank + 2 : d->nranks];
+	s->slab_bounds.assign(bounds, bounds + d->nranks + 1);
+	// (the handle holds no tracers here: a block of its single-domain past has no room for ids, the next add allocates one that has)
+	for (void **b : {&s->tracers.base, &s->tracers.alt}) {
+		if (*b) (void)hipFree(*b);
+		*b = nullptr;
+	}
+	s->tracers.cap = s->tracers.alt_cap = 0;
+	s->tracers.first_id = 0;
 	s->binned = false;
 	s->sources_valid = false;  // the seeding entries are the ones of this rank's own tile layers ...
 	s->sources_built.clear();  // ... so entries flattened for another range (the whole domain, earlier bounds) are not "the same list"

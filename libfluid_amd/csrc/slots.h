@@ -70,7 +70,11 @@ enum {
 	LFA_PIN_SAMPLE_OWNED = 106,      // lfa_sample_velocity_collective: points this rank owns ...
 	LFA_PIN_SAMPLE_OUTSIDE = 107,    // ... and points outside the grid
 	LFA_PIN_TRACER_COUNTS = 108,     // lfa_tracers_step: tracers stopped in the march, and (109) tracers frozen
-	LFA_PIN_COUNT = 110,
+	LFA_PIN_TRACER_KEPT = 110,       // lfa_tracers_add_collective: tracers of the list this rank keeps
+	LFA_PIN_TRACER_MIGRATE = 112,    // tracers.hip, a round of the slab migration: leaving down / up, staying, arriving from
+	                                 // below / above, lowest / highest destination layer (int32) [112, 119)
+	LFA_PIN_TRACER_ROUNDS = 120,     // ... and the job's round count, a double [120, 122)
+	LFA_PIN_COUNT = 122,
 	LFA_PIN_BYTES = 4096,            // the allocation
 };
 static_assert(LFA_PIN_STATE + LFA_DW_READBACK_WORDS <= LFA_PIN_SLAB && LFA_PIN_SLAB + LFA_SLAB_WORDS <= LFA_PIN_N_UNKNOWNS,
@@ -78,6 +82,9 @@ static_assert(LFA_PIN_STATE + LFA_DW_READBACK_WORDS <= LFA_PIN_SLAB && LFA_PIN_S
 static_assert(LFA_PIN_LAST_RESIDUAL % 2 == 0 && LFA_PIN_LAST_RESIDUAL + 2 <= LFA_PIN_NP_LIVE, "h_pinned: the residual is an aligned double");
 static_assert(LFA_PIN_N_DTILES == LFA_PIN_N_PTILES + 1, "h_pinned: the two tile counts arrive as one block");
 static_assert(LFA_PIN_MG_COUNTS + LFA_MAX_MG_LEVELS <= LFA_PIN_SOURCE_TOTAL, "h_pinned: the level counts run into the next claim");
+static_assert(LFA_PIN_TRACER_KEPT >= LFA_PIN_TRACER_COUNTS + 2 && LFA_PIN_TRACER_MIGRATE + 7 <= LFA_PIN_TRACER_ROUNDS &&
+                  LFA_PIN_TRACER_ROUNDS % 2 == 0 && LFA_PIN_TRACER_ROUNDS + 2 <= LFA_PIN_COUNT,
+              "h_pinned: the tracer migration's words overlap, or its round count is no aligned double");
 static_assert(LFA_PIN_COUNT * 4 <= LFA_PIN_BYTES, "h_pinned: a claim lies beyond the allocation");
 
 // ---------------------------------------------------------------------------------------------------- lfa_sim::dist_red
@@ -92,12 +99,16 @@ enum {
 	                            // below; each of the three is written, reduced and read back inside one call
 	LFA_DR_MIGRATE_COUNTS = 32,  // dist.hip, lfa_dist_migrate: five uint32 - leaving lo / hi, arriving from lo / hi, beyond reach
 	LFA_DR_GHOST_TOTALS = 40,   // dist.hip, ghost particles: two uint32 - arriving from below / above
+	LFA_DR_TRACER_ROUNDS = 42,  // tracers.hip, lfa_tracers_advect_collide_collective: the job's round count (max over the ranks' hop
+	                            // distances) and, behind it, this rank's own [42, 44)
 	LFA_DR_GATHER = 64,         // two gather buffers (parity), each [max | sum | sum2 per rank | given up]: lfa_dist_gather_buf
 	LFA_DR_GATHER_LEN = 3 * LFA_DR_MAX_RANKS + 1,
 	LFA_DR_ALPHA = LFA_DR_GATHER + 2 * LFA_DR_GATHER_LEN,  // alpha of the single-reduction CG (2) and room behind it
 	LFA_DR_COUNT = LFA_DR_ALPHA + 8,
 };
 static_assert(LFA_DR_SIGMA + 2 <= LFA_DR_SOURCE_TOTALS && LFA_DR_GHOST_TOTALS + 1 <= LFA_DR_GATHER, "dist_red: scalars overlap");
+static_assert(LFA_DR_GHOST_TOTALS + 1 <= LFA_DR_TRACER_ROUNDS && LFA_DR_TRACER_ROUNDS + 2 <= LFA_DR_GATHER && LFA_DR_GATHER <= LFA_DR_COUNT,
+              "dist_red: the tracer round count overlaps another claim or lies beyond the allocation");
 
 // ---------------------------------------------------------------------------------------------------- lfa_sim::pcg_hist
 enum {
